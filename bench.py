@@ -3,6 +3,7 @@
 unlabelled, NEU-Seg-shaped 256x256 4-class, K=3 auxiliary decoders = 4 heads).
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py ... --dump-outputs DIR                 (also writes what the last timed step computed: dump_outputs)
 
 A step = UAPSTrainer.train_step on one synthetic batch pair resident in HBM (16 labelled + 16
 unlabelled images per GPU, config[1] of BASELINE.json): two forwards, fused HIP loss block, backward,
@@ -383,6 +384,39 @@ def spawn_ranks(n):
     return 0 if not bad else (bad[0] if bad[0] > 0 else 1)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, trainer):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy (float32 / float64): the step's scalars
+    (loss.npy, sup.npy, unsup.npy), its head-mixing and consistency weights, the main head's confusion matrix on the labelled
+    batch, and the model state the step left behind (state.<state_dict key>.npy: parameters after Adam, BatchNorm running
+    statistics).  Two builds run with the same arguments get the same inputs, so their dumps compare array for array.  When the
+    state exceeds the budget, every state tensor keeps the same fixed, seeded sample of its elements (state.<key>.sample.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    last = trainer.last
+    arrays = {k: np.asarray(last[k].detach().float().cpu().numpy(), np.float32) for k in ("loss", "sup", "unsup")}
+    arrays["mix_weights"] = np.asarray(last["w"], np.float64)
+    arrays["consistency_weights"] = np.asarray([last["cw1"], last["cw2"]], np.float64)
+    if trainer._cms:
+        arrays["confusion"] = trainer._cms[-1].cpu().numpy().astype(np.float64)
+    state = {k: v.detach() for k, v in trainer.model.state_dict().items() if v.is_floating_point()}
+    total = sum(v.numel() * 4 for v in state.values())
+    frac = min(1.0, (DUMP_BUDGET_BYTES - (1 << 20)) / max(total, 1))     # 1 MB kept for the arrays above and the .npy headers
+    rng = np.random.default_rng(0)
+    for k, v in state.items():
+        a = v.float().cpu().numpy()
+        if frac < 1.0:
+            idx = np.sort(rng.choice(a.size, max(1, int(a.size * frac)), replace=False))
+            arrays[f"state.{k}.sample"] = a.ravel()[idx]
+        else:
+            arrays[f"state.{k}"] = a
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -407,7 +441,11 @@ def main():
     ap.add_argument("--no-power-log", action="store_true", help="do not start tools/power_sampler.py (clock / socket power across the timed regions)")
     ap.add_argument("--other-configs", type=int, default=4,
                     help="N = 1 only: steps timed of each of BASELINE.json configs[3] and the per-GPU shape of configs[4] after everything else (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # not under a launcher: this process becomes one (it has touched no GPU and imports no torch) and exits with the job's code
@@ -534,6 +572,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     last_loss = float(trainer.last["loss"])
+    if args.dump_outputs and rank == 0:            # before the passes below step the model on
+        dump_outputs(args.dump_outputs, trainer)
     sg = trainer.step_graph
     graph_used = sg is not None and sg.graph is not None        # False: no capture asked for, too few warm-up steps, or a failed capture
     graph_split = graph_used and sg.split

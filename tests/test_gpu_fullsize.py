@@ -257,34 +257,43 @@ def _float64_and_float32_oracle_step(B, H, W, C):
     keeps = {"l": [], "u": []}
     real_fd = O.feature_dropout
     res = {}
-    for dt in (torch.float64, torch.float32):
-        sd = {k: (v.detach().clone().to(dt) if v.is_floating_point() else v.detach().clone()) for k, v in sd0.items()}
-        for k in sd:
-            if sd[k].is_floating_point() and (k.endswith(".weight") or k.endswith(".bias")):
-                sd[k].requires_grad_(True)
-        rr = {t: {"noise": [n.to(dt) for n in d["noise"]], "mask": [m.to(dt) for m in d["mask"]], "u": d["u"]} for t, d in rec.items()}
+    threads = torch.get_num_threads()
+    try:
+        for dt in (torch.float64, torch.float32):
+            # The float32 run's summation order follows torch's CPU thread count (the convolutions and reductions split their sums by
+            # thread), and with it which pool ties and LeakyReLU signs flip, i.e. the bar the test derives from this run: its median
+            # gradient error from float64 at B = 16 measured 1.22e-3 on one thread, 1.16e-3 on 16 or 128.  One thread: the same
+            # order whatever thread count the host gives the process.
+            torch.set_num_threads(1 if dt == torch.float32 else threads)
+            sd = {k: (v.detach().clone().to(dt) if v.is_floating_point() else v.detach().clone()) for k, v in sd0.items()}
+            for k in sd:
+                if sd[k].is_floating_point() and (k.endswith(".weight") or k.endswith(".bias")):
+                    sd[k].requires_grad_(True)
+            rr = {t: {"noise": [n.to(dt) for n in d["noise"]], "mask": [m.to(dt) for m in d["mask"]], "u": d["u"]} for t, d in rec.items()}
 
-        def fd_for(tag):
-            if dt == torch.float64:                 # record the keep masks ...
-                def fd(x, u):
-                    att = x.mean(dim=1, keepdim=True)
-                    thr = (att.reshape(x.shape[0], -1).max(dim=1, keepdim=True)[0] * float(u)).view(-1, 1, 1, 1)
-                    keeps[tag].append((att < thr))
-                    return x * keeps[tag][-1].to(x.dtype)
-                return fd
-            it = iter(keeps[tag])                   # ... and replay them
-            return lambda x, u: x * next(it).to(x.dtype)
-        try:
-            O.feature_dropout = fd_for("l")
-            lab = O.uaps_forward(xl.to(dt), sd, True, rr["l"], dropout=[0.0] * 5)
-            O.feature_dropout = fd_for("u")
-            un = O.uaps_forward(xu.to(dt), sd, True, rr["u"], dropout=[0.0] * 5)
-        finally:
-            O.feature_dropout = real_fd
-        r = O.step_loss(un, lab, yl, w, cw1, cw2)
-        r["loss"].backward()
-        res[dt] = {"lab": [t.detach() for t in lab], "un": [t.detach() for t in un], "loss": float(r["loss"].detach()),
-                   "grads": {k: sd[k].grad.detach().double() for k in sd if sd[k].is_floating_point() and sd[k].grad is not None}}
+            def fd_for(tag):
+                if dt == torch.float64:                 # record the keep masks ...
+                    def fd(x, u):
+                        att = x.mean(dim=1, keepdim=True)
+                        thr = (att.reshape(x.shape[0], -1).max(dim=1, keepdim=True)[0] * float(u)).view(-1, 1, 1, 1)
+                        keeps[tag].append((att < thr))
+                        return x * keeps[tag][-1].to(x.dtype)
+                    return fd
+                it = iter(keeps[tag])                   # ... and replay them
+                return lambda x, u: x * next(it).to(x.dtype)
+            try:
+                O.feature_dropout = fd_for("l")
+                lab = O.uaps_forward(xl.to(dt), sd, True, rr["l"], dropout=[0.0] * 5)
+                O.feature_dropout = fd_for("u")
+                un = O.uaps_forward(xu.to(dt), sd, True, rr["u"], dropout=[0.0] * 5)
+            finally:
+                O.feature_dropout = real_fd
+            r = O.step_loss(un, lab, yl, w, cw1, cw2)
+            r["loss"].backward()
+            res[dt] = {"lab": [t.detach() for t in lab], "un": [t.detach() for t in un], "loss": float(r["loss"].detach()),
+                       "grads": {k: sd[k].grad.detach().double() for k in sd if sd[k].is_floating_point() and sd[k].grad is not None}}
+    finally:
+        torch.set_num_threads(threads)
     out = (sd0, xl, xu, yl, w, rec, keeps, cw1, cw2, res)
     _F64_CACHE[key] = out
     return out
@@ -313,11 +322,12 @@ def test_real_width_step_256_vs_float64_oracle(mode):
     worst <= 3 x the float32 oracle's, over all parameters -- a composed error of 23 layers of 22-bit operand pieces (mode
     h16) that exceeded fp32's would show here.  FeatureDropout's keep mask is a step function of the features
     (UAPS_unet.py:161-169), so the masks the float64 oracle drew are replayed everywhere (the threshold logic itself is pinned
-    bit for bit by fixture g3).  The default arithmetic (h16) runs at the metric's own batch, 16 + 16 images of 256 x 256; the two
-    other modes at 4 + 4 (UAPS_TEST_F64_BATCH overrides both)."""
+    bit for bit by fixture g3).  All three arithmetics run at the metric's own batch, 16 + 16 images of 256 x 256, on one pair of
+    oracle runs (UAPS_TEST_F64_BATCH overrides it).  At 4 + 4 images the medians rest on a handful of such flips: the float32
+    oracle's own median there moved from 5.6e-4 to 7.6e-4 with nothing but the CPU thread count, 1.16e-3 to 1.22e-3 at 16 + 16."""
     import os
     from uaps_amd import conv, losses, perturb, unet
-    B, H, W, C = int(os.environ.get("UAPS_TEST_F64_BATCH", "16" if mode == "h16" else "4")), 256, 256, 4
+    B, H, W, C = int(os.environ.get("UAPS_TEST_F64_BATCH", "16")), 256, 256, 4
     sd0, xl, xu, yl, w, rec, keeps, cw1, cw2, res = _float64_and_float32_oracle_step(B, H, W, C)
     r64, r32 = res[torch.float64], res[torch.float32]
     model = unet.UNet_UAPS(3, C, n_aux=3, dropout=[0.0] * 5)

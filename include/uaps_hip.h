@@ -587,10 +587,15 @@ typedef struct uaps_conv_call {
                                           * must not exceed what struct_size leaves for it */
 } uaps_conv_call;
 int uaps_conv_ex(const uaps_conv_call* call);
+/* The name (as rocprofv3 prints it, without namespace) of the kernel instantiation uaps_conv_ex(call) launches, nothing launched and
+ * no HIP call made: the same struct, resolved exactly as the launch resolves it (data pointers are looked at for their alignment
+ * only; the workspace size is not checked).  buf_host needs >= 64 bytes.  A call that has no kernel returns the code uaps_conv_ex
+ * would return (UAPS_ENOFORM for a hint no form honours, ...).  bench.py names each timed launch by it. */
+int uaps_conv_ex_variant(const uaps_conv_call* call, char* buf_host, size_t buflen);
 
 /* Name (as rocprofv3 prints it, without namespace) of the kernel instantiation the calls above launch
- * for these dimensions; buf_host needs >= 64 bytes.  For uaps_conv_bwd_data pass Cin and Cout swapped
- * to uaps_conv_fwd_variant.  Used by bench.py to group its per-launch HIP-event timings. */
+ * for these dimensions with 16-byte aligned tensors and no hints (uaps_conv_ex_variant with null pointers); buf_host needs
+ * >= 64 bytes.  For uaps_conv_bwd_data pass Cin and Cout swapped to uaps_conv_fwd_variant. */
 int uaps_conv_fwd_variant(int B, int Cin, int Cout, int H, int W, int ks, int cfg, char* buf_host, size_t buflen);
 int uaps_conv_wrw_variant(int B, int Cin, int Cout, int H, int W, int ks, int cfg, char* buf_host, size_t buflen);
 int uaps_conv_bwd_weight(const float* dy, const float* x, float* dw, float* dbias, int B, int Cin, int Cout, int H,

@@ -198,3 +198,107 @@ def test_explicit_hints_forms_validate_their_record(L):
     # uaps_conv_call: `stream` sits in front of the growable hints record (ABI 3)
     assert _lib.ConvCall.stream.offset < _lib.ConvCall.hints.offset
     assert _lib.ConvCall.hints.offset + C.sizeof(_lib.CallHints) == C.sizeof(_lib.ConvCall)
+
+
+FWD, BWD_DATA, WRW, ENOFORM = 0, 1, 2, -4
+FAKE = 1 << 20                                   # 16-byte aligned, never dereferenced: uaps_conv_ex_variant launches nothing
+BOUNDED = 1 << 11
+
+
+def _call(op, B, Cin, Cout, H, W, ks=3, cfg=0, bounds=0, **fields):
+    """A uaps_conv_call with fake aligned operands and, for the first `bounds` operands, fake bound pointers."""
+    c = _lib.ConvCall(struct_size=C.sizeof(_lib.ConvCall), op=op, B=B, Cin=Cin, Cout=Cout, H=H, W=W, ks=ks, cfg=cfg)
+    c.x = c.y = c.w_packed = c.y_grad = c.workspace = FAKE
+    c.hints.struct_size = C.sizeof(_lib.CallHints)
+    for i in range(bounds):
+        c.hints.bound[i], c.hints.mul[i] = FAKE + 4096 * (i + 1), 1.0
+    for k, v in fields.items():
+        setattr(c, k, v)
+    return c
+
+
+def _variant(L, c):
+    buf = C.create_string_buffer(96)
+    rc = L.uaps_conv_ex_variant(C.byref(c), buf, 96)
+    return buf.value.decode() if rc == OK else rc
+
+
+@pytest.fixture
+def h16_mode(L):
+    L.uaps_conv_get_tuning.restype = C.c_uint
+    prev_mode, prev_tune = L.uaps_conv_get_mode(), L.uaps_conv_get_tuning()
+    assert L.uaps_conv_set_mode(2) == OK and L.uaps_conv_set_tuning(0) == OK
+    yield
+    L.uaps_conv_set_mode(prev_mode)
+    L.uaps_conv_set_tuning(prev_tune)
+
+
+def test_ex_variant_names_the_kernel_of_the_whole_call(L, h16_mode):
+    """uaps_conv_ex_variant resolves a uaps_conv_call exactly as uaps_conv_ex does -- bounds, statistics, staging-time BatchNorm,
+    the pending-BatchNorm transform, a second tensor -- and names the kernel it would launch, without a GPU."""
+    parts = C.c_int()
+    # bounded 16 -> 16 on a 256-wide map with statistics: the full-width-row kernel, in the layout uaps_conv_fwd_stats_parts reports
+    assert L.uaps_conv_fwd_stats_parts(8, 16, 16, 256, 256, 3, BOUNDED, C.byref(parts)) == OK and parts.value == 32 * 8
+    assert _variant(L, _call(FWD, 8, 16, 16, 256, 256, cfg=BOUNDED, bounds=1, stats=FAKE)) == "conv_hr16_kernel<2>"
+    assert _variant(L, _call(FWD, 8, 16, 16, 256, 256, stats=FAKE)) == "conv_sfwd_kernel<3, 8, 32, 16, 16>"      # no bounds: bf16 pieces
+    # up1's input gradient: 128 -> 128 + 128 channels at W = 32 -- the 32x32x16 form, not the whole-layer-width kernel (that needs
+    # exactly 128 output channels)
+    up1 = dict(C1=128, y2=FAKE + 65536)
+    assert _variant(L, _call(BWD_DATA, 32, 256, 128, 32, 32, bounds=1, **up1)) == "conv_h32_kernel<64>"
+    assert _variant(L, _call(BWD_DATA, 32, 256, 128, 32, 32, **up1)) == "conv_s32_kernel<64>"
+    # 128 -> 128 at W = 32, bounded, no statistics: the whole-layer-width kernel; with the staging-time BatchNorm the tile kernels
+    assert _variant(L, _call(FWD, 32, 128, 128, 32, 32, bounds=1)) == "conv_hg128_kernel"
+    bn = _variant(L, _call(FWD, 32, 128, 128, 32, 32, bounds=1, xf=FAKE, xf_slope=0.01, xf_groups=1))
+    assert bn.startswith("conv_h") and "_bn_" in bn and "hg128" not in bn, bn
+    assert _variant(L, _call(FWD, 32, 128, 128, 32, 32)).startswith("conv_sfwd_kernel<")
+    # the weight gradient that forms dy from the pending BatchNorm transform (dyt_*) at 256^2: the row kernel's DT form
+    dyt = dict(dyt_y=FAKE + 8192, dyt_coef=FAKE + 12288, dyt_out=FAKE + 16384, dyt_slope=0.01, dyt_groups=1)
+    c = _call(WRW, 8, 16, 16, 256, 256, bounds=2)
+    assert _variant(L, c) == "conv_hrwrw_kernel<1>"
+    for k, v in dyt.items():
+        setattr(c.hints, k, v)
+    assert _variant(L, c) == "conv_hrwrw_dt_kernel<1>"
+    assert _variant(L, _call(WRW, 8, 16, 16, 256, 256)) == "conv_swrw_kernel<4, 1, 1>"
+    c = _call(WRW, 8, 16, 16, 256, 256)
+    for k, v in dyt.items():
+        setattr(c.hints, k, v)
+    assert _variant(L, c) == ENOFORM                                                     # no bounds: no row kernel, no DT form
+    # uaps_conv_fwd_variant / _wrw_variant are the same query with null pointers and no hints
+    buf = C.create_string_buffer(96)
+    assert L.uaps_conv_fwd_variant(32, 128, 128, 32, 32, 3, 0, buf, 96) == OK and buf.value.decode() == _variant(L, _call(FWD, 32, 128, 128, 32, 32))
+    assert L.uaps_conv_wrw_variant(8, 16, 16, 256, 256, 3, 0, buf, 96) == OK and buf.value.decode() == "conv_swrw_kernel<4, 1, 1>"
+
+
+def test_ex_variant_returns_the_code_of_a_call_without_form(L, h16_mode):
+    """A request that no kernel of the shape honours is refused before anything is launched, with the launch's return code."""
+    bsum = dict(bsum_y=FAKE, bsum_mean=FAKE, bsum_invstd=FAKE, bsum_gamma=FAKE, bsum_beta=FAKE, bsum_partials=FAKE, bsum_max=FAKE,
+                bsum_slope=0.01, bsum_groups=1)
+    c = _call(BWD_DATA, 8, 16, 16, 256, 256, bounds=1)
+    for k, v in bsum.items():
+        setattr(c.hints, k, v)
+    assert _variant(L, c) == "conv_hr16_bs_kernel"                                       # the one shape with the epilogue sums
+    c = _call(BWD_DATA, 8, 32, 32, 128, 128, bounds=1)
+    for k, v in bsum.items():
+        setattr(c.hints, k, v)
+    assert _variant(L, c) == ENOFORM
+    up2 = 1 << 10                                                                        # UAPS_CONV_X2_UP2
+    assert _variant(L, _call(FWD, 8, 32, 16, 256, 256, cfg=up2, bounds=2, C1=16, x2=FAKE)) == "conv_hr16_up_kernel"
+    assert _variant(L, _call(WRW, 8, 32, 16, 256, 256, cfg=up2, bounds=3, C1=16, x2=FAKE)) == "conv_hrwrw_up_kernel"
+    assert _variant(L, _call(FWD, 8, 64, 32, 128, 128, cfg=up2, bounds=2, C1=32, x2=FAKE)) == ENOFORM
+    assert _variant(L, _call(WRW, 8, 64, 32, 128, 128, cfg=up2, bounds=3, C1=32, x2=FAKE)) == ENOFORM
+    c = _call(FWD, 32, 128, 128, 32, 32, bounds=1)
+    c.hints.out_amax = FAKE + 4096 * 8
+    assert _variant(L, c) == ENOFORM                                                     # out_amax: fp32-instruction forms only
+
+
+def test_statistics_layout_mismatches_are_refused(L, h16_mode):
+    """With UAPS_CONV_BOUNDED, uaps_conv_fwd_stats_parts reports the whole-layer-width kernel's layout (one part per 4-row band) for
+    128 output channels at W = 32.  A call of that shape that cannot run that kernel -- a concatenation split that is not a multiple
+    of 32, a second tensor that is not 16-byte aligned -- would write another layout: UAPS_ERANGE, nothing launched."""
+    parts = C.c_int()
+    assert L.uaps_conv_fwd_stats_parts(4, 128, 128, 32, 32, 3, BOUNDED, C.byref(parts)) == OK and parts.value == 8
+    cat = dict(cfg=BOUNDED, bounds=2, stats=FAKE)
+    assert _variant(L, _call(FWD, 4, 128, 128, 32, 32, C1=32, x2=FAKE + 65536, **cat)) == "conv_hg128_kernel"
+    assert _variant(L, _call(FWD, 4, 128, 128, 32, 32, C1=16, x2=FAKE + 65536, **cat)) == ERANGE
+    assert _variant(L, _call(FWD, 4, 128, 128, 32, 32, C1=32, x2=FAKE + 65540, **cat)) == ERANGE
+    assert _variant(L, _call(FWD, 4, 128, 128, 32, 32, C1=16, x2=FAKE + 65536, bounds=2, stats=FAKE)).startswith("conv_h")   # no promise: tile layout

@@ -646,3 +646,34 @@ def test_whole_width_tile_form_equals_the_tile_kernels(B, H):
     for n, u, v in zip(names, new, old):
         scale = float(v.abs().max()) + 1e-12
         assert float((u - v).abs().max()) <= 3e-5 * scale, (n, float((u - v).abs().max()) / scale)
+
+
+def test_statistics_layout_mismatch_is_refused_before_launch(conv_mode):
+    """With UAPS_CONV_BOUNDED, uaps_conv_fwd_stats_parts reports the whole-layer-width kernel's partials layout (one part per 4-row
+    band) for 128 output channels at W = 32.  A concatenation that cannot run that kernel -- a split that is not a multiple of 32, a
+    second tensor that is not 16-byte aligned -- would have written the 8 x 32-tile layout into that buffer: it returns
+    UAPS_ERANGE and leaves output and partials untouched; the aligned 32 + 96 split runs."""
+    if conv_mode != "h16":
+        pytest.skip("the whole-width tile form exists in the fp16-split arithmetic only")
+    from uaps_amd import _lib, bounds, conv
+    dev = torch.device("cuda:0")
+    torch.manual_seed(5)
+    B, Cin, Cout, H, W = 4, 128, 128, 32, 32
+    wf, _ = conv.pack_weights(torch.randn(Cout, Cin, 3, 3, device=dev) / 30)
+    ppi = conv.stats_parts_per_image(B, Cin, Cout, H, W, 3, conv.BOUNDED)
+    assert ppi == H // 4
+    L = _lib.lib()
+    for C1, offset, want in ((16, 0, -2), (16, 1, -2), (32, 1, -2), (32, 0, 0)):
+        C2 = Cin - C1
+        x1 = torch.randn(B, C1, H, W, device=dev)
+        buf = torch.randn(B * C2 * H * W + 4, device=dev)
+        x2 = buf[offset:offset + B * C2 * H * W].view(B, C2, H, W)          # offset 1: 4 bytes past a 16-byte boundary
+        y = torch.full((B, Cout, H, W), 7.0, device=dev)
+        stats = torch.full((Cout, B, ppi, 2), 7.0, device=dev)
+        hh = _lib.mk_hints(((bounds.from_value(x1.abs().max()), 1.0), (bounds.from_value(x2.abs().max()), 1.0)))
+        rc = L.uaps_conv_fwd_cat_h(hh, x1.data_ptr(), C1, x2.data_ptr(), C2, wf.data_ptr(), None, y.data_ptr(), stats.data_ptr(),
+                                   B, Cout, H, W, 3, conv.BOUNDED, _lib.current_stream(dev))
+        torch.cuda.synchronize()
+        assert rc == want, (C1, offset, rc)
+        untouched = bool((y == 7.0).all()) and bool((stats == 7.0).all())
+        assert untouched == (want != 0), (C1, offset)

@@ -85,6 +85,7 @@ SIGNATURES = {
     "uaps_set_step_state": (C.c_int, [_PTR]),
     "uaps_next_call_hints": (C.c_int, [_PTR]),
     "uaps_conv_ex": (C.c_int, [_PTR]),
+    "uaps_conv_ex_variant": (C.c_int, [_PTR, C.c_char_p, C.c_size_t]),
     "uaps_account": (C.c_int, [C.c_int]),
     "uaps_accounted_bytes": (C.c_double, []),
     "uaps_next_launch_events": (C.c_int, [_PTR, _PTR]),

@@ -75,89 +75,54 @@ ENOFORM = -4                      # UAPS_ENOFORM (include/uaps_hip.h)
 
 
 def kernel_variant(kind: str, B: int, Cin: int, Cout: int, H: int, W: int, ks: int, cfg: int = 0) -> str:
-    """Name of the kernel instantiation a call launches ('fwd' / 'bwd_data' / 'wrw'), as rocprofv3 prints it."""
+    """Name of the kernel instantiation a call of these dimensions launches ('fwd' / 'bwd_data' / 'wrw') with aligned tensors and no
+    hints, as rocprofv3 prints it."""
     key = (kind, B, Cin, Cout, H, W, ks, cfg)
     name = _variant_cache.get(key)
     if name is None:
         buf = C.create_string_buffer(96)
         L = _lib.lib()
-        if kind in ("wrw", "wrw_bn"):
+        if kind == "wrw":
             rc = L.uaps_conv_wrw_variant(B, Cin, Cout, H, W, ks, cfg, buf, 96)
         elif kind == "bwd_data":
             rc = L.uaps_conv_fwd_variant(B, Cout, Cin, H, W, ks, cfg, buf, 96)
         else:
             rc = L.uaps_conv_fwd_variant(B, Cin, Cout, H, W, ks, cfg, buf, 96)
         _lib.check(rc, "uaps_conv_*_variant")
-        name = buf.value.decode()
-        if kind.endswith("_bn"):      # the variants that apply BatchNorm + LeakyReLU while staging (fused._BnActConv)
-            name = (name.replace("conv_fwd_kernel", "conv_fwd_bn_kernel").replace("conv_wrw_kernel", "conv_wrw_bn_kernel")
-                    .replace("conv_sfwd_kernel", "conv_sfwd_bn_kernel").replace("conv_s32_kernel", "conv_s32_bn_kernel").replace("conv_s32t_kernel", "conv_s32t_bn_kernel").replace("conv_swrw_kernel", "conv_swrw_bn_kernel")
-                    .replace("conv_small_kernel", "conv_small_bn_kernel").replace("conv_small_wrw_kernel", "conv_small_wrw_bn_kernel"))
-        _variant_cache[key] = name
+        name = _variant_cache[key] = buf.value.decode()
     return name
 
 
+FWD, BWD_DATA, WRW = 0, 1, 2      # UAPS_CONV_FWD / _BWD_DATA / _BWD_WEIGHT (include/uaps_hip.h)
+
+
 class _timed:
-    def __init__(self, kind, B, Cin, Cout, H, W, ks, cfg, h16=False, stats=False, dt=False, name=None):
+    """While KERNEL_EVENTS collects, times the main kernel of one convolution call under the name uaps_conv_ex_variant gives for the
+    same call: `hints` as handed to the launch, the operands by uaps_conv_call field name.  A call without a kernel records nothing."""
+
+    def __init__(self, op, B, Cin, Cout, H, W, ks, cfg, hints=None, **tensors):
         self.on = False
-        if KERNEL_EVENTS is not None and name is not None:      # the caller knows the instantiation (the up-sampling forms)
-            self.name = name.replace("_kernel", "_dt_kernel", 1) if dt else name
-            self.on = EVENT_FILTER is None or self.name in EVENT_FILTER
-            self.flops = 2.0 * B * H * W * Cin * Cout * ks * ks
-        elif KERNEL_EVENTS is not None:
-            self.name = kernel_variant(kind, B, Cin, Cout, H, W, ks, cfg)
-            if stats and self.name.startswith("conv_small"):      # the exact-N kernels have no statistics epilogue: the matrix kernel ran
-                self.name = kernel_variant(kind, B, Cin, Cout, H, W, ks, cfg | (1 << 28))
-            if h16:                   # every tensor operand carried a bound: the fp16 two-piece instantiation of the same plan ran
-                kin = Cout if kind == "bwd_data" else Cin
-                if (self.name.startswith("conv_small_") and "wrw" not in self.name and W % 256 == 0 and H % 16 == 0 and kin in (16, 24, 32)
-                        and not (_lib.lib().uaps_conv_get_tuning() & (128 | 8))):
-                    # <= 4 output channels on a 256-wide map: the full-width-row kernel (csrc/conv_fwd.hip: row16)
-                    self.name = ("conv_hr16%s_bn_kernel" if "_bn_" in self.name else "conv_hr16%s_kernel") % ("w" if W > 256 else "") + ("<2>" if kin <= 16 else "<4>")
-                if self.name.startswith("conv_sfwd") and "<3, 8, 32, 16," in self.name and 8 < kin <= 32:
-                    # <= 16 output channels on a wide map: the persistent kernels of csrc/conv_split_n16.hpp
-                    row = W % 256 == 0 and H % 16 == 0 and not (_lib.lib().uaps_conv_get_tuning() & 128)      # csrc/conv_fwd.hip: launch_hr16
-                    fam = ("r16w" if W > 256 else "r16") if row else "p16"      # wider than 256: the column-strip instantiations
-                    self.name = ("conv_h%s_bn_kernel" if "_bn_" in self.name else "conv_h%s_kernel") % fam + ("<2>" if kin <= 16 else "<4>")
-                if (kind == "bwd_data" and ks == 3 and kin == 16 and Cin == 32 and W % 256 == 0 and H % 16 == 0 and self.name.startswith("conv_s32")
-                        and not (_lib.lib().uaps_conv_get_tuning() & (128 | 8))):
-                    self.name = "conv_hr16wx2_kernel" if W > 256 else "conv_hr16x2_kernel"       # 16 -> 16 + 16 channels: two output tiles of the full-width-row kernel
-                kout = Cin if kind == "bwd_data" else Cout
-                if (kind in ("fwd", "fwd_bn", "bwd_data") and ks == 3 and W == 32 and H % 4 == 0 and kin % 32 == 0 and kout % 128 == 0
-                        and not (cfg & 0x7fffffff & ~BOUNDED) and (not stats or (cfg & BOUNDED))
-                        and (self.name.startswith("conv_s32") or self.name.startswith("conv_sfwd"))
-                        and not (_lib.lib().uaps_conv_get_tuning() & 2048)):
-                    # 128-output-channel layers on 32-wide maps: the whole-layer-width tile form (csrc/conv_split_g.hpp; csrc/conv_fwd.hip: g128)
-                    self.name = "conv_hg128_bn_kernel" if "_bn_" in self.name else "conv_hg128_kernel"
-                self.name = (self.name.replace("conv_s32", "conv_h32").replace("conv_sfwd", "conv_hfwd").replace("conv_swrw", "conv_hwrw")
-                             .replace("conv_g1s", "conv_g1h").replace("conv_gw1s", "conv_gw1h"))
-                if self.name == "conv_g1h_kernel<128>" and (Cin if kind == "bwd_data" else Cout) % 256 == 0 and not (_lib.lib().uaps_conv_get_tuning() & 1024):
-                    self.name = "conv_g1h256_kernel"       # 256 output channels per workgroup (csrc/conv_fwd.hip: launch_g1)
-                if (kind in ("wrw", "wrw_bn") and ks == 3 and W % 256 == 0 and H % 16 == 0 and Cout <= 16 and Cin <= 32 and not (cfg >> 24)
-                        and (self.name.startswith("conv_hwrw") or self.name.startswith("conv_small_wrw") or self.name.startswith("conv_wrw_"))
-                        and not (_lib.lib().uaps_conv_get_tuning() & (256 | 2))):
-                    # the full-width-row weight-gradient kernels (csrc/conv_split_wrw_row.hpp; csrc/conv_wrw.hip: the eligibility block)
-                    self.name = ("conv_hrwrw%s_bn_kernel<%d>" if "_bn_" in self.name else "conv_hrwrw%s_kernel<%d>") % ("w" if W > 256 else "", 1 if Cin <= 16 else 2)
-                if self.name.startswith("conv_hwrw") and "_kernel<4, 1, " in self.name and H >= 8 and not (_lib.lib().uaps_conv_get_tuning() & 32):
-                    self.name = self.name.replace("_kernel<4, 1, ", "_kernel<8, 1, ")      # 16 output channels: the 8-row tiles (csrc/conv_wrw.hip: launch_swrw)
-                if self.name.startswith("conv_wrw_kernel<3, 4, 32, 2, 2, 4, ") and not self.name.endswith(" 1>") and W >= 32 and Cin >= 16:
-                    self.name = "conv_hwrw_d_kernel<4, 2, 2, " + self.name.split(",")[-1].strip()      # the dilated fp16 form (csrc/conv_wrw.hip)
-            if dt:                    # the forms that turn d(activation) into dy while staging (uaps_call_hints::dyt_*)
-                self.name = self.name.replace("_kernel", "_dt_kernel", 1)
-            self.on = EVENT_FILTER is None or self.name in EVENT_FILTER
-            self.flops = 2.0 * B * H * W * Cin * Cout * ks * ks
+        if KERNEL_EVENTS is not None:
+            c = _lib.ConvCall(struct_size=C.sizeof(_lib.ConvCall), op=op, B=B, Cin=Cin, Cout=Cout, H=H, W=W, ks=ks, cfg=cfg)
+            for k, v in tensors.items():
+                setattr(c, k, v.data_ptr() if isinstance(v, torch.Tensor) else v)
+            if hints is not None:
+                c.hints = hints._obj
+            buf = C.create_string_buffer(96)
+            if _lib.lib().uaps_conv_ex_variant(C.byref(c), buf, 96) == 0:
+                self.name = buf.value.decode()
+                self.on = EVENT_FILTER is None or self.name in EVENT_FILTER
+                self.flops = 2.0 * B * H * W * Cin * Cout * ks * ks
 
     def __enter__(self):
-        self.armed = self.on
         if self.on:
             self.t = _lib.LaunchTimer().__enter__()
         return self
 
     def __exit__(self, *a):
-        if self.armed:                # (a caller clears `on` when the entry point launched nothing: disarm, record nothing)
+        if self.on:
             self.t.__exit__()
-            if self.on:
-                KERNEL_EVENTS.setdefault(self.name, []).append((self.t.start, self.t.stop, self.flops))
+            KERNEL_EVENTS.setdefault(self.name, []).append((self.t.start, self.t.stop, self.flops))
         return False
 
 
@@ -654,24 +619,23 @@ def conv_fwd_raw(x: torch.Tensor, wf: torch.Tensor, bias: Optional[torch.Tensor]
     L = _lib.lib()
     bp = bias.data_ptr() if bias is not None else None
     cfg = plan_cfg(ks, cfg, True, x, y)
+    stats = None
     if want_stats:
         cfg = stats_cfg(cfg, xb)
         ppi = stats_parts_per_image(B, Cin, Cout, H, W, ks, cfg)
         stats = torch.empty((Cout, B, ppi, 2), dtype=torch.float32, device=x.device)
     am = _claim_amax(x.device)
     for attempt in range(2):
-        with _lib.device_guard(x.device), _timed("fwd", B, Cin, Cout, H, W, ks, cfg, _h16(xb), want_stats) as tm:
-            hh = None
-            if xb is not None or (want_stats and stat_shift is not None) or am is not None:
-                hh = _lib.mk_hints((xb,) if xb is not None else (), am, stat_shift if want_stats else None)
+        hh = None
+        if xb is not None or (want_stats and stat_shift is not None) or am is not None:
+            hh = _lib.mk_hints((xb,) if xb is not None else (), am, stat_shift if want_stats else None)
+        with _lib.device_guard(x.device), _timed(FWD, B, Cin, Cout, H, W, ks, cfg, hh, x=x, y=y, stats=stats):
             if want_stats:
                 rc = L.uaps_conv_fwd_stats_h(hh, x.data_ptr(), wf.data_ptr(), bp, y.data_ptr(), stats.data_ptr(), B, Cin, Cout, H, W, ks, cfg,
                                              _lib.current_stream(x.device))
             else:
                 rc = L.uaps_conv_fwd_h(hh, x.data_ptr(), wf.data_ptr(), bp, y.data_ptr(), B, Cin, Cout, H, W, ks, cfg,
                                        _lib.current_stream(x.device))
-            if rc == ENOFORM:
-                tm.on = False
         if rc != ENOFORM or am is None:
             break
         am = None                                     # this layer's kernel cannot track max|y|: run it without (the caller falls back)
@@ -702,18 +666,16 @@ def conv_bwd_data_raw(dy: torch.Tensor, wb: torch.Tensor, Cin: int, ks: int, cfg
         maxes = torch.empty(2 * bounds.FLOATS, dtype=torch.float32, device=dev)
         with _lib.device_guard(dev):
             _lib.check(L.uaps_zero_bounds(maxes.data_ptr(), maxes.numel(), _lib.current_stream(dev)), "uaps_zero_bounds")
-            with _timed("bwd_data", B, Cin, Cout, H, W, ks, cfg, True, name="conv_hr16_bs_kernel") as tm:
-                rc = L.uaps_conv_bwd_data_h(_lib.mk_hints((dyb,), bsum=(bsum[0], bsum[1], bsum[2], bsum[3], bsum[4], partials, maxes, bsum[5], bsum[6])),
-                                            dy.data_ptr(), wb.data_ptr(), dx.data_ptr(), B, Cin, Cout, H, W, ks, cfg, _lib.current_stream(dev))
-                if rc == ENOFORM:
-                    tm.on = False
+            hh = _lib.mk_hints((dyb,), bsum=(bsum[0], bsum[1], bsum[2], bsum[3], bsum[4], partials, maxes, bsum[5], bsum[6]))
+            with _timed(BWD_DATA, B, Cin, Cout, H, W, ks, cfg, hh, x=dy, y=dx):
+                rc = L.uaps_conv_bwd_data_h(hh, dy.data_ptr(), wb.data_ptr(), dx.data_ptr(), B, Cin, Cout, H, W, ks, cfg, _lib.current_stream(dev))
         if rc != ENOFORM:
             _lib.check(rc, "uaps_conv_bwd_data")
             return dx, partials, maxes
         partials = maxes = None
-    with _lib.device_guard(dev), _timed("bwd_data", B, Cin, Cout, H, W, ks, cfg, _h16(dyb)):
-        rc = L.uaps_conv_bwd_data_h(_lib.mk_hints((dyb,)) if dyb is not None else None,
-                                    dy.data_ptr(), wb.data_ptr(), dx.data_ptr(), B, Cin, Cout, H, W, ks, cfg, _lib.current_stream(dev))
+    hh = _lib.mk_hints((dyb,)) if dyb is not None else None
+    with _lib.device_guard(dev), _timed(BWD_DATA, B, Cin, Cout, H, W, ks, cfg, hh, x=dy, y=dx):
+        rc = L.uaps_conv_bwd_data_h(hh, dy.data_ptr(), wb.data_ptr(), dx.data_ptr(), B, Cin, Cout, H, W, ks, cfg, _lib.current_stream(dev))
     _lib.check(rc, "uaps_conv_bwd_data")
     return (dx, None, None) if bsum is not None else dx
 
@@ -740,20 +702,19 @@ def conv_bwd_weight_raw(dy: torch.Tensor, x: torch.Tensor, ks: int, want_bias: b
         rc = lazybn.ENOFORM
         if lz is not None and xb is not None:
             dy_true = torch.empty_like(dy)
-            with _timed("wrw", B, Cin, Cout, H, W, ks, cfg, True, dt=True) as tm:
-                rc = L.uaps_conv_bwd_weight_partial_h(_lib.mk_hints((lz.bound, xb), dyt=(lz.y, lz.coef, dy_true, lz.slope, lz.groups)),
-                                                      dy.data_ptr(), x.data_ptr(), int(want_bias), B, Cin, Cout, H, W, ks, cfg,
+            hh = _lib.mk_hints((lz.bound, xb), dyt=(lz.y, lz.coef, dy_true, lz.slope, lz.groups))
+            with _timed(WRW, B, Cin, Cout, H, W, ks, cfg, hh, y_grad=dy, x=x):
+                rc = L.uaps_conv_bwd_weight_partial_h(hh, dy.data_ptr(), x.data_ptr(), int(want_bias), B, Cin, Cout, H, W, ks, cfg,
                                                       ws.data_ptr(), ws.numel(), st)
-                tm.on = tm.on and rc != lazybn.ENOFORM
             if rc != lazybn.ENOFORM:
                 bounds.put(dy_true, *lz.bound)
         if lz is not None and rc == lazybn.ENOFORM:
             dy_true = dy = lazybn.materialize(dy, lz)
             dyb = bounds.get(dy)
         if lz is None or rc == lazybn.ENOFORM:
-            with _timed("wrw", B, Cin, Cout, H, W, ks, cfg, _h16(dyb, xb)):
-                rc = L.uaps_conv_bwd_weight_partial_h(_lib.mk_hints((dyb, xb)) if (dyb is not None and xb is not None) else None,
-                                                      dy.data_ptr(), x.data_ptr(), int(want_bias), B, Cin, Cout, H, W, ks, cfg,
+            hh = _lib.mk_hints((dyb, xb)) if (dyb is not None and xb is not None) else None
+            with _timed(WRW, B, Cin, Cout, H, W, ks, cfg, hh, y_grad=dy, x=x):
+                rc = L.uaps_conv_bwd_weight_partial_h(hh, dy.data_ptr(), x.data_ptr(), int(want_bias), B, Cin, Cout, H, W, ks, cfg,
                                                       ws.data_ptr(), ws.numel(), st)
         _lib.check(rc, "uaps_conv_bwd_weight_partial")
         _wrw_reduce(ws, dw, db, B, Cin, Cout, H, W, ks, cfg, st, prefs, step)
@@ -872,10 +833,10 @@ class _Conv2dCat(torch.autograd.Function):
         if want_stats:
             stats = torch.empty((Cout, B, stats_parts_per_image(B, Cin, Cout, H, W, ks, fcfg), 2), dtype=torch.float32, device=dev)
         ucfg = fcfg | (X2_UP2 if up2 else 0)
-        with _lib.device_guard(dev), _timed("fwd", B, Cin, Cout, H, W, ks, fcfg, _h16(b1, b2), want_stats, name="conv_hr16_up_kernel" if up2 else None):
-            hh = None
-            if (b1 is not None and b2 is not None) or (want_stats and stat_shift is not None):
-                hh = _lib.mk_hints((b1, b2) if (b1 is not None and b2 is not None) else (), None, stat_shift if want_stats else None)
+        hh = None
+        if (b1 is not None and b2 is not None) or (want_stats and stat_shift is not None):
+            hh = _lib.mk_hints((b1, b2) if (b1 is not None and b2 is not None) else (), None, stat_shift if want_stats else None)
+        with _lib.device_guard(dev), _timed(FWD, B, Cin, Cout, H, W, ks, ucfg, hh, x=x1, C1=C1, x2=x2, y=y, stats=stats):
             rc = _lib.lib().uaps_conv_fwd_cat_h(hh, x1.data_ptr(), C1, x2.data_ptr(), C2, wf.data_ptr(),
                                                 bias.data_ptr() if bias is not None else None, y.data_ptr(),
                                                 stats.data_ptr() if want_stats else None, B, Cout, H, W, ks, ucfg, _lib.current_stream(dev))
@@ -925,17 +886,14 @@ class _Conv2dCat(torch.autograd.Function):
             dw = _graddest.take(ctx.keys[0], (Cout, C1 + C2, ks, ks), dev)
             db = _graddest.take(ctx.keys[1], (Cout,), dev) if want_db else None
             out = torch.empty_like(dy) if lz is not None else None
-            with _timed("wrw", B, C1 + C2, Cout, H, W, ks, cfg, _h16(dyb, b1, b2), dt=lz is not None,
-                        name="conv_hrwrw_up_kernel" if ucfg != cfg else None) as tm:
-                hh = None
-                if lz is not None:
-                    hh = _lib.mk_hints((dyb, b1, b2), dyt=(lz.y, lz.coef, out, lz.slope, lz.groups))
-                elif dyb is not None and b1 is not None and b2 is not None:
-                    hh = _lib.mk_hints((dyb, b1, b2))
+            hh = None
+            if lz is not None:
+                hh = _lib.mk_hints((dyb, b1, b2), dyt=(lz.y, lz.coef, out, lz.slope, lz.groups))
+            elif dyb is not None and b1 is not None and b2 is not None:
+                hh = _lib.mk_hints((dyb, b1, b2))
+            with _timed(WRW, B, C1 + C2, Cout, H, W, ks, ucfg, hh, y_grad=dy, x=x1, C1=C1, x2=x2w):
                 rc = L.uaps_conv_bwd_weight_partial_cat_h(hh, dy.data_ptr(), x1.data_ptr(), C1, x2w.data_ptr(), C2, int(want_db), B, Cout,
                                                           H, W, ks, ucfg, ws.data_ptr(), ws.numel(), st)
-                if lz is not None and rc == lazybn.ENOFORM:
-                    tm.on = False
             if lz is not None and rc == lazybn.ENOFORM:
                 return None, None, None
             _lib.check(rc, "uaps_conv_bwd_weight_partial_cat")
@@ -956,9 +914,9 @@ class _Conv2dCat(torch.autograd.Function):
             if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
                 dx1 = torch.empty_like(x1)
                 dx2 = torch.empty((B, C2, H, W), dtype=torch.float32, device=dev) if up2 else torch.empty_like(x2)
-                with _timed("bwd_data", B, C1 + C2, Cout, H, W, ks, cfg, _h16(dyb)):
-                    rc = L.uaps_conv_bwd_data_cat_h(_lib.mk_hints((dyb,)) if dyb is not None else None,
-                                                    dy.data_ptr(), wb.data_ptr(), dx1.data_ptr(), C1, dx2.data_ptr(), C2, B, Cout, H, W,
+                hh = _lib.mk_hints((dyb,)) if dyb is not None else None
+                with _timed(BWD_DATA, B, C1 + C2, Cout, H, W, ks, cfg, hh, x=dy, y=dx1, C1=C1, y2=dx2):
+                    rc = L.uaps_conv_bwd_data_cat_h(hh, dy.data_ptr(), wb.data_ptr(), dx1.data_ptr(), C1, dx2.data_ptr(), C2, B, Cout, H, W,
                                                     ks, cfg, st)
                 _lib.check(rc, "uaps_conv_bwd_data_cat")
             if want_w and not done_w:

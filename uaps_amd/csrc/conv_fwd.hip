@@ -11,6 +11,7 @@
 #include "conv_gemm1x1.hpp"
 #include "conv_split_g.hpp"
 #include "hints.hpp"
+#include "conv_call.hpp"
 using namespace uaps;
 
 // 0 = exact fp32 matrix instructions (v_mfma_f32_16x16x4_f32), 1 = exact 3-way bf16 split on the bf16 matrix pipe,
@@ -34,212 +35,6 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline int kdim_pad(int c, int ks) { return (ks == 3 && c <= 4) ? 4 : round_up(c, 8); }   // K (contraction) channels: chunk of 4 or 8
 inline int ndim_pad(int c) { return round_up(c, 16); }              // N (output) channels: 16-wide MFMA tiles
 
-template <int KS, int TH, int TW, int BN, int CK, int DIL = 1>
-int launch_fwd(ConvFwdArgs a, bool vec, int extra_lds, hipStream_t s) {
-    a.tiles_x = (a.W + TW - 1) / TW;
-    a.tiles_y = (a.H + TH - 1) / TH;
-    a.nblk = a.CoutP / BN;
-    const long grid = ((long)a.B * a.tiles_x * a.tiles_y * a.nblk + 7) / 8 * 8;   // multiple of 8 for the XCD swizzle
-    if (grid <= 0 || grid > 0x7fffffffL) return UAPS_EINVAL;
-    // extra_lds: unused dynamic LDS, requested only to cap the number of co-resident workgroups per CU
-    if (a.xf) {                  // BatchNorm + LeakyReLU of the input applied while staging: 16-byte form, 8-channel chunks, no dilation
-        if constexpr (DIL == 1 && CK == 8) {
-            if (!vec) return UAPS_ERANGE;
-            UAPS_LAUNCH_MAIN((conv_fwd_bn_kernel<KS, TH, TW, BN, CK, 4, 1>), dim3((unsigned)grid), dim3(kConvThreads), extra_lds, s, a);
-            return (int)hipGetLastError();
-        } else {
-            return UAPS_ERANGE;
-        }
-    }
-    if (vec) UAPS_LAUNCH_MAIN((conv_fwd_kernel<KS, TH, TW, BN, CK, 4, DIL>), dim3((unsigned)grid), dim3(kConvThreads), extra_lds, s, a);
-    else UAPS_LAUNCH_MAIN((conv_fwd_kernel<KS, TH, TW, BN, CK, 1, DIL>), dim3((unsigned)grid), dim3(kConvThreads), extra_lds, s, a);
-    return (int)hipGetLastError();
-}
-
-template <int KS, int TH, int TW>
-int dispatch_bn_ck(const ConvFwdArgs& a, int bn, int ck, bool vec, int xl, hipStream_t s) {
-    if constexpr (KS == 3) {
-        if (ck == 4) return launch_fwd<KS, TH, TW, 16, 4>(a, vec, xl, s);
-    }
-    if (bn == 16) return launch_fwd<KS, TH, TW, 16, 8>(a, vec, xl, s);
-    if (bn == 32) return launch_fwd<KS, TH, TW, 32, 8>(a, vec, xl, s);
-    return launch_fwd<KS, TH, TW, 64, 8>(a, vec, xl, s);
-}
-
-// dilated 3x3 (ResNet stages with stride replaced by dilation): 8x32 tiles, 8-channel chunks
-template <int DIL>
-int dispatch_dilated(const ConvFwdArgs& a, int bn, bool vec, int xl, hipStream_t s) {
-    if (bn == 16) return launch_fwd<3, 8, 32, 16, 8, DIL>(a, vec, xl, s);
-    if (bn == 32) return launch_fwd<3, 8, 32, 32, 8, DIL>(a, vec, xl, s);
-    return launch_fwd<3, 8, 32, 64, 8, DIL>(a, vec, xl, s);
-}
-
-// ---- split-bf16 kernels (conv_split.hpp): 16-byte rows only, no dilation ----
-template <int KS, int TH, int TW, int BN, int CK>
-int launch_sfwd(ConvFwdArgs a, hipStream_t s) {
-    a.tiles_x = (a.W + TW - 1) / TW;
-    a.tiles_y = (a.H + TH - 1) / TH;
-    a.nblk = a.CoutP / BN;
-    const long grid = ((long)a.B * a.tiles_x * a.tiles_y * a.nblk + 7) / 8 * 8;
-    if (grid <= 0 || grid > 0x7fffffffL) return UAPS_EINVAL;
-    if (a.wscale) {                                   // the fp16 two-piece form (plan: h16)
-        if (a.xf) UAPS_LAUNCH_MAIN((conv_hfwd_bn_kernel<KS, TH, TW, BN, CK>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-        else UAPS_LAUNCH_MAIN((conv_hfwd_kernel<KS, TH, TW, BN, CK>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-        return (int)hipGetLastError();
-    }
-    if (a.xf) UAPS_LAUNCH_MAIN((conv_sfwd_bn_kernel<KS, TH, TW, BN, CK>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-    else UAPS_LAUNCH_MAIN((conv_sfwd_kernel<KS, TH, TW, BN, CK>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-    return (int)hipGetLastError();
-}
-template <int KS, int TH, int TW>
-int dispatch_sfwd(const ConvFwdArgs& a, int bn, int ck, hipStream_t s) {
-    if constexpr (KS == 3) {
-        if (ck == 8) return bn == 16 ? launch_sfwd<3, TH, TW, 16, 8>(a, s) : launch_sfwd<3, TH, TW, 32, 8>(a, s);
-        return bn == 16 ? launch_sfwd<3, TH, TW, 16, 16>(a, s) : launch_sfwd<3, TH, TW, 32, 16>(a, s);
-    } else {
-        return bn == 16 ? launch_sfwd<1, TH, TW, 16, 32>(a, s) : launch_sfwd<1, TH, TW, 32, 32>(a, s);
-    }
-}
-
-// persistent 16-output-channel kernels of conv_split_n16.hpp (fp16 form only): each workgroup takes a run of tiles
-int launch_hp16(ConvFwdArgs a, hipStream_t s) {
-    a.tiles_x = (a.W + 31) / 32;
-    a.tiles_y = (a.H + 7) / 8;
-    a.nblk = 1;
-    const long ntiles = (long)a.B * a.tiles_x * a.tiles_y;
-    if (ntiles <= 0 || ntiles > 0x7fffffffL) return UAPS_EINVAL;
-    // one resident round: 3 (16 input channels) or 2 (32) workgroups fit a CU (registers), 256 CUs; forcing 4 spills and is slower
-    const long want = a.Cin <= 16 ? 768 : 512;
-    const unsigned grid = (unsigned)(((ntiles < want ? ntiles : want) + 7) / 8 * 8);
-    if (a.Cin <= 16) {
-        if (a.xf) UAPS_LAUNCH_MAIN((conv_hp16_bn_kernel<2>), dim3(grid), dim3(kConvThreads), 0, s, a);
-        else UAPS_LAUNCH_MAIN((conv_hp16_kernel<2>), dim3(grid), dim3(kConvThreads), 0, s, a);
-    } else {
-        if (a.xf) UAPS_LAUNCH_MAIN((conv_hp16_bn_kernel<4>), dim3(grid), dim3(kConvThreads), 0, s, a);
-        else UAPS_LAUNCH_MAIN((conv_hp16_kernel<4>), dim3(grid), dim3(kConvThreads), 0, s, a);
-    }
-    return (int)hipGetLastError();
-}
-
-// full-width-row kernels of conv_split_row16.hpp (fp16 form, maps of 256 pixels width -- or a multiple: 256-wide column strips --, H % 16 == 0): runs of 16 rows, 2 workgroups of
-// 256 threads per CU for 16 input channels, 1 workgroup of 512 threads (135 KB of LDS) for 32
-int launch_hr16(ConvFwdArgs a, hipStream_t s) {
-    const long nruns = (long)a.B * (a.H / 16) * (a.W / 256);      // a run: 16 rows of one 256-wide column strip
-    if (nruns <= 0 || nruns > 0x7fffffffL) return UAPS_EINVAL;
-    const long want = a.Cin <= 16 ? 512 : 256;
-    const unsigned grid = (unsigned)(((nruns < want ? nruns : want) + 7) / 8 * 8);
-    const bool strips = a.W > 256;
-    if (a.Cin <= 16) {
-        if (strips) {
-            if (a.xf) UAPS_LAUNCH_MAIN((conv_hr16w_bn_kernel<2>), dim3(grid), dim3(256), 0, s, a);
-            else UAPS_LAUNCH_MAIN((conv_hr16w_kernel<2>), dim3(grid), dim3(256), 0, s, a);
-        } else {
-            if (a.xf) UAPS_LAUNCH_MAIN((conv_hr16_bn_kernel<2>), dim3(grid), dim3(256), 0, s, a);
-            else UAPS_LAUNCH_MAIN((conv_hr16_kernel<2>), dim3(grid), dim3(256), 0, s, a);
-        }
-    } else {
-        if (strips) {
-            if (a.xf) UAPS_LAUNCH_MAIN((conv_hr16w_bn_kernel<4>), dim3(grid), dim3(512), 0, s, a);
-            else UAPS_LAUNCH_MAIN((conv_hr16w_kernel<4>), dim3(grid), dim3(512), 0, s, a);
-        } else {
-            if (a.xf) UAPS_LAUNCH_MAIN((conv_hr16_bn_kernel<4>), dim3(grid), dim3(512), 0, s, a);
-            else UAPS_LAUNCH_MAIN((conv_hr16_kernel<4>), dim3(grid), dim3(512), 0, s, a);
-        }
-    }
-    return (int)hipGetLastError();
-}
-
-// 16 + 16 -> 16 channels, the second 16 up-sampled x2 from a low-resolution tensor while staging (conv_hr16_up_kernel; W == 256)
-int launch_hr16_up(ConvFwdArgs a, hipStream_t s) {
-    const long nruns = (long)a.B * (a.H / 16);
-    if (nruns <= 0 || nruns > 0x7fffffffL) return UAPS_EINVAL;
-    const int h = a.H / 2, w = a.W / 2;
-    a.up_rh = (float)(h - 1) / (float)(a.H - 1); a.up_rw = (float)(w - 1) / (float)(a.W - 1);      // as uaps_up_cat_fwd
-    const unsigned grid = (unsigned)(((nruns < 256 ? nruns : 256) + 7) / 8 * 8);
-    UAPS_LAUNCH_MAIN(conv_hr16_up_kernel, dim3(grid), dim3(512), 0, s, a);
-    return (int)hipGetLastError();
-}
-
-// 16 -> 16 channels, 256 wide: the input gradient that also forms the BatchNorm-backward sums of the layer in front (conv_hr16_bs_kernel)
-int launch_hr16_bs(ConvFwdArgs a, hipStream_t s) {
-    const long nruns = (long)a.B * (a.H / 16);
-    if (nruns <= 0 || nruns > 0x7fffffffL) return UAPS_EINVAL;
-    const unsigned grid = (unsigned)(((nruns < 512 ? nruns : 512) + 7) / 8 * 8);
-    UAPS_LAUNCH_MAIN(conv_hr16_bs_kernel, dim3(grid), dim3(256), 0, s, a);
-    return (int)hipGetLastError();
-}
-
-int launch_hr16x2(ConvFwdArgs a, hipStream_t s) {
-    const long nruns = (long)a.B * (a.H / 16) * (a.W / 256);
-    if (nruns <= 0 || nruns > 0x7fffffffL) return UAPS_EINVAL;
-    const unsigned grid = (unsigned)(((nruns < 512 ? nruns : 512) + 7) / 8 * 8);
-    if (a.W > 256) UAPS_LAUNCH_MAIN(conv_hr16wx2_kernel, dim3(grid), dim3(256), 0, s, a);
-    else UAPS_LAUNCH_MAIN(conv_hr16x2_kernel, dim3(grid), dim3(256), 0, s, a);
-    return (int)hipGetLastError();
-}
-
-int launch_g1(ConvFwdArgs a, int bn, hipStream_t s) {
-    a.tiles_x = (a.H * a.W + 127) / 128;
-    a.tiles_y = 1;
-    a.nblk = a.CoutP / bn;
-    const long grid = ((long)a.B * a.tiles_x * a.nblk + 7) / 8 * 8;
-    if (grid <= 0 || grid > 0x7fffffffL) return UAPS_EINVAL;
-    if (a.wscale) {
-        if (bn == 256) UAPS_LAUNCH_MAIN(conv_g1h256_kernel, dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-        else if (bn == 128) UAPS_LAUNCH_MAIN((conv_g1h_kernel<128>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-        else UAPS_LAUNCH_MAIN((conv_g1h_kernel<64>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-    } else {
-        if (bn == 128) UAPS_LAUNCH_MAIN((conv_g1s_kernel<128>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-        else UAPS_LAUNCH_MAIN((conv_g1s_kernel<64>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-    }
-    return (int)hipGetLastError();
-}
-
-int launch_small(ConvFwdArgs a, int kind, hipStream_t s) {
-    a.tiles_x = (a.W + 63) / 64;
-    a.tiles_y = (a.H + 15) / 16;
-    a.nblk = 1;
-    const long grid = ((long)a.B * a.tiles_x * a.tiles_y + 7) / 8 * 8;
-    if (grid <= 0 || grid > 0x7fffffffL) return UAPS_EINVAL;
-    (void)kind;
-    if (a.xf) UAPS_LAUNCH_MAIN((conv_small_bn_kernel<8, 4>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-    else UAPS_LAUNCH_MAIN((conv_small_kernel<8, 4>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-    return (int)hipGetLastError();
-}
-
-template <int BN>
-int launch_s32(ConvFwdArgs a, hipStream_t s) {
-    a.tiles_x = (a.W + 31) / 32;
-    a.tiles_y = (a.H + 7) / 8;
-    a.nblk = a.CoutP / BN;
-    const long grid = ((long)a.B * a.tiles_x * a.tiles_y * a.nblk + 7) / 8 * 8;
-    if (grid <= 0 || grid > 0x7fffffffL) return UAPS_EINVAL;
-    if (a.wscale) {                                   // the fp16 two-piece form (plan: h16)
-        if (a.xf) UAPS_LAUNCH_MAIN((conv_h32_bn_kernel<BN>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-        else UAPS_LAUNCH_MAIN((conv_h32_kernel<BN>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-        return (int)hipGetLastError();
-    }
-    if (a.xf) UAPS_LAUNCH_MAIN((conv_s32_bn_kernel<BN>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-    else UAPS_LAUNCH_MAIN((conv_s32_kernel<BN>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-    return (int)hipGetLastError();
-}
-
-// 16-row tiles, 32 output channels per workgroup (conv_s32t/h32t kernels)
-int launch_s32t(ConvFwdArgs a, hipStream_t s) {
-    a.tiles_x = (a.W + 31) / 32;
-    a.tiles_y = (a.H + 15) / 16;
-    a.nblk = a.CoutP / 32;
-    const long grid = ((long)a.B * a.tiles_x * a.tiles_y * a.nblk + 7) / 8 * 8;
-    if (grid <= 0 || grid > 0x7fffffffL) return UAPS_EINVAL;
-    if (a.wscale) {
-        if (a.xf) UAPS_LAUNCH_MAIN((conv_h32t_bn_kernel<32>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-        else UAPS_LAUNCH_MAIN((conv_h32t_kernel<32>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-        return (int)hipGetLastError();
-    }
-    if (a.xf) UAPS_LAUNCH_MAIN((conv_s32t_bn_kernel<32>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-    else UAPS_LAUNCH_MAIN((conv_s32t_kernel<32>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-    return (int)hipGetLastError();
-}
 
 // split: one of the bf16-split kernels runs; s32: the 32x32x16 form (3x3, 8x32 tiles, >= 32 output channels)
 // small: 1 = the exact-N VALU kernel for <= 4 output channels (conv_small.hpp)
@@ -324,165 +119,383 @@ int plan_fwd(const void* x, const void* y, int B, int Cin, int Cout, int H, int 
     return UAPS_OK;
 }
 
-int launch_hg128(ConvFwdArgs a, hipStream_t s) {
-    a.tiles_x = 1;
-    a.tiles_y = a.H / 4;
-    a.nblk = a.Cout / 128;
-    const long grid = ((long)a.B * a.tiles_y * a.nblk + 7) / 8 * 8;
-    if (grid <= 0 || grid > 0x7fffffffL) return UAPS_EINVAL;
-    static bool attr = false;
-    if (!attr) {                                      // (idempotent; > 48 KB of dynamic LDS needs the attribute once per kernel)
-        (void)hipFuncSetAttribute((const void*)conv_hg128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kHg128Lds);
-        (void)hipFuncSetAttribute((const void*)conv_hg128_bn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kHg128Lds);
-        (void)hipFuncSetAttribute((const void*)conv_hg128_deep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kHg128Lds);
-        attr = true;
-    }
-    if (a.xf) UAPS_LAUNCH_MAIN(conv_hg128_bn_kernel, dim3((unsigned)grid), dim3(kHg128Threads), kHg128Lds, s, a);
-    else if (g_conv_tuning & UAPS_TUNE_G_DEEP) UAPS_LAUNCH_MAIN(conv_hg128_deep_kernel, dim3((unsigned)grid), dim3(kHg128Threads), kHg128Lds, s, a);
-    else UAPS_LAUNCH_MAIN(conv_hg128_kernel, dim3((unsigned)grid), dim3(kHg128Threads), kHg128Lds, s, a);
-    return (int)hipGetLastError();
-}
-
-template <int BN>
-int launch_s32d(ConvFwdArgs a, int dil, hipStream_t s) {
-    a.tiles_x = (a.W + 31) / 32;
-    a.tiles_y = (a.H + 7) / 8;
-    a.nblk = a.CoutP / BN;
-    const long grid = ((long)a.B * a.tiles_x * a.tiles_y * a.nblk + 7) / 8 * 8;
-    if (grid <= 0 || grid > 0x7fffffffL || (dil != 2 && dil != 4)) return UAPS_EINVAL;
-    if (a.wscale) {
-        if (dil == 2) UAPS_LAUNCH_MAIN((conv_h32d_kernel<BN, 2>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-        else UAPS_LAUNCH_MAIN((conv_h32d_kernel<BN, 4>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-    } else {
-        if (dil == 2) UAPS_LAUNCH_MAIN((conv_s32d_kernel<BN, 2>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-        else UAPS_LAUNCH_MAIN((conv_s32d_kernel<BN, 4>), dim3((unsigned)grid), dim3(kConvThreads), 0, s, a);
-    }
-    return (int)hipGetLastError();
-}
-
-// x [B,Cin,H,W] * packed weights [taps][CinP][CoutP] -> y [B,Cout,H,W]
-// x2 / Csplit: optional second input tensor holding channels [Csplit, Cin); y2 / Osplit likewise for the output
-int conv_fwd_any(const uaps_call_hints& hints, const float* x, const float* wp, const float* bias, float* y, int B, int Cin, int Cout, int H, int W, int ks,
-                 int cfg, hipStream_t s, float2* stats = nullptr, const float* x2 = nullptr, int Csplit = -1,
-                 float* y2 = nullptr, int Osplit = -1, const void* xf = nullptr, float xf_slope = 0.f, int groups = 1) {
-    if (!x || !wp || !y) return UAPS_EINVAL;
-    // UAPS_CONV_X2_UP2: x2 is [B, Cin - Csplit, H / 2, W / 2] and is up-sampled x2 (bilinear, align_corners) while staged
-    const bool up2 = (cfg & UAPS_CONV_X2_UP2) != 0;
-    cfg &= ~UAPS_CONV_X2_UP2;
-    if (up2 && (!x2 || H % 2 || W % 2)) return UAPS_EINVAL;
-    if (xf && (x2 || groups < 1 || B % groups || (uintptr_t)xf % 8)) return UAPS_EINVAL;
-    if (xf && !(xf_slope >= 0.f && xf_slope <= 1.f)) return UAPS_ERANGE;      // leaky_relu is evaluated as max(z, slope * z)
-    if (Csplit < 0 || !x2) Csplit = Cin;
-    if (Osplit < 0 || !y2) Osplit = Cout;
-    if (Csplit > Cin || Osplit > Cout || (Csplit < Cin && (Csplit % 8 || Csplit == 0)) || (Osplit < Cout && Osplit == 0)) return UAPS_EINVAL;
+// uaps_conv_fwd_stats_parts: the BatchNorm-partials layout that shape and cfg alone decide -- one part per pixel tile of the plan, per
+// 128 pixels of the GEMM-tiled plan, or (UAPS_CONV_BOUNDED) per 4-row band of the whole-layer-width plan (conv_split_g.hpp)
+int stats_parts(int B, int Cin, int Cout, int H, int W, int ks, int cfg, int* parts) {
     FwdPlan p{};
-    const int rc = plan_fwd(x, y, B, Cin, Cout, H, W, ks, cfg, &p);
+    const int rc = plan_fwd(nullptr, nullptr, B, Cin, Cout, H, W, ks, cfg, &p);
     if (rc) return rc;
-    if ((x2 && !up2 && (uintptr_t)x2 % 16) || (y2 && (uintptr_t)y2 % 16)) p.vec = false;
+    *parts = (p.g128 && p.bounded) ? H / 4 : p.g1 ? (H * W + 127) / 128 : ((H + p.th - 1) / p.th) * ((W + p.tw - 1) / p.tw);
+    return UAPS_OK;
+}
+
+// The kernel forms of the forward / input gradient (each a family of conv_*_kernel instantiations; the split forms come as 's' = three
+// bf16 pieces and 'h' = two fp16 pieces, most also with the staging-time BatchNorm of xf: `_bn`)
+enum class FwdKind {
+    Tile,      // conv_fwd_kernel<ks, th, tw, n, ck, vec, dil>: the fp32 matrix instruction
+    Small,     // conv_small_kernel<8, 4>: the exact-N VALU kernel (<= 4 output channels)
+    Split,     // conv_sfwd / conv_hfwd_kernel<ks, th, tw, n, ck>
+    S32,       // conv_s32 / conv_h32_kernel<n>: the 32x32x16 form, 8 x 32 tiles
+    S32T,      // conv_s32t / conv_h32t_kernel<32>: 16-row tiles
+    S32D,      // conv_s32d / conv_h32d_kernel<n, dil>: dilated
+    G1,        // conv_g1s_kernel<n>, conv_g1h_kernel<n>, conv_g1h256_kernel: GEMM-tiled 1x1
+    HG128,     // conv_hg128_kernel (conv_hg128_deep_kernel): one workgroup per 4-row band x 128 channels
+    HP16,      // conv_hp16_kernel<n>: persistent, 16 output channels
+    HR16,      // conv_hr16_kernel<n> (conv_hr16w_kernel: 256-wide column strips): full-width rows, 16 output channels
+    HR16Up,    // conv_hr16_up_kernel: x2 up-sampled while staged (UAPS_CONV_X2_UP2)
+    HR16Bs,    // conv_hr16_bs_kernel: BatchNorm-backward sums in the epilogue (uaps_call_hints::bsum_*)
+    HR16x2,    // conv_hr16x2_kernel (conv_hr16wx2_kernel): 16 -> 32 channels as two output tiles
+};
+
+// What one call runs: the kernel with its template parameters, the launch geometry and the BatchNorm-partials layout it writes
+struct FwdForm {
+    FwdPlan plan;
+    FwdKind kind;
+    int ks, th, tw, n, ck, dil;        // template parameters (n: output channels per workgroup; HP16 / HR16: 2 or 4)
+    bool vec, h16, bn, deep, strips;   // 16-byte rows; fp16 pieces; staging-time BatchNorm; HG128 deep; HR16 column strips
+    bool up2;
+    int Csplit, Osplit;                // the concatenation splits (Cin / Cout: one tensor)
+    unsigned grid, block; int lds;
+    int tiles_x, tiles_y, nblk;
+    int parts;                         // BatchNorm partials per image
+};
+
+bool split_form(FwdKind k) { return k != FwdKind::Tile && k != FwdKind::Small; }
+unsigned grid8(long n) { return (unsigned)((n + 7) / 8 * 8); }      // a multiple of 8 for the XCD swizzle
+
+// Which kernel the call runs.  Every condition of that choice is here, host code only (no HIP call): a query needs no GPU.  The
+// optional requests (up2, bsum, out_amax, stats) that only some forms honour are checked against the result by check_fwd.
+int resolve_fwd(const uaps_call_hints& h, const FwdCall& c, FwdForm* out) {
+    const int B = c.B, Cin = c.Cin, Cout = c.Cout, H = c.H, W = c.W, ks = c.ks;
+    const void* xf = c.xf;
+    // UAPS_CONV_X2_UP2: x2 is [B, Cin - Csplit, H / 2, W / 2] and is up-sampled x2 (bilinear, align_corners) while staged
+    const bool up2 = (c.cfg & UAPS_CONV_X2_UP2) != 0;
+    const int cfg = c.cfg & ~UAPS_CONV_X2_UP2;
+    if (up2 && (!c.x2 || H % 2 || W % 2)) return UAPS_EINVAL;
+    if (xf && (c.x2 || c.groups < 1 || B % c.groups || (uintptr_t)xf % 8)) return UAPS_EINVAL;
+    if (xf && !(c.xf_slope >= 0.f && c.xf_slope <= 1.f)) return UAPS_ERANGE;      // leaky_relu is evaluated as max(z, slope * z)
+    const int Csplit = (c.Csplit < 0 || !c.x2) ? Cin : c.Csplit;
+    const int Osplit = (c.Osplit < 0 || !c.y2) ? Cout : c.Osplit;
+    if (Csplit > Cin || Osplit > Cout || (Csplit < Cin && (Csplit % 8 || Csplit == 0)) || (Osplit < Cout && Osplit == 0)) return UAPS_EINVAL;
+    FwdForm f{};
+    FwdPlan& p = f.plan;
+    const int rc = plan_fwd(c.x, c.y, B, Cin, Cout, H, W, ks, cfg, &p);
+    if (rc) return rc;
+    if ((c.x2 && !up2 && (uintptr_t)c.x2 % 16) || (c.y2 && (uintptr_t)c.y2 % 16)) p.vec = false;
     if (!p.vec || (Csplit < Cin && Csplit % p.sck)) p.split = false;      // unaligned tensors / odd concat split: exact kernels
-    if (p.dil > 1 && (!p.s32 || x2 || y2 || xf)) p.split = false;        // the dilated split form: one tensor per side, no staging BatchNorm
-    // uaps_conv_fwd_stats_parts reported the GEMM-tiled plan's parts (shape alone decides it); a call that cannot run that plan
-    // must not write another layout.  The Python layer never gets here: conv.plan_cfg hands such calls cfg bit 28.
-    if (stats) {
-        FwdPlan p0{};
-        if (plan_fwd(nullptr, nullptr, B, Cin, Cout, H, W, ks, cfg, &p0)) return UAPS_EINVAL;
-        if (p0.g1 != (p.g1 && p.split && !x2 && !y2 && !xf)) return UAPS_ERANGE;
-    }
-    uaps::account_bytes(4.0 * B * H * W * ((double)Csplit + (Cin - Csplit) * (up2 ? 0.25 : 1.0) + Cout));      // every input and output element once
-    ConvFwdArgs a{};
-    a.in = x; a.in2 = x2; a.Csplit = Csplit; a.out2 = y2; a.Osplit = Osplit;
-    a.wp = wp; a.bias = bias; a.out = y; a.stats = stats;
-    if (stats) { a.stats_mean = hints.stats_mean; a.stats_bias = hints.stats_bias; } a.B = B; a.Cin = Cin; a.Cout = Cout; a.H = H; a.W = W;
-    a.CinP = p.CinP; a.CoutP = p.CoutP;
-    a.xf = (const float2*)xf; a.xf_slope = xf_slope; a.xf_Bg = xf ? B / groups : B;
-    // out_amax: raised to max|y| by the fp32-instruction kernels only (the U-Net's 1x1 projections, whose output has no BatchNorm
-    // behind it to bound it); a plan that runs another kernel has no such form
-    if (hints.out_amax) {
-        if (p.split || p.small || p.g1 || (uintptr_t)hints.out_amax % 16) return UAPS_ENOFORM;
-        a.amax = hints.out_amax;
-    }
+    if (p.dil > 1 && (!p.s32 || c.x2 || c.y2 || xf)) p.split = false;    // the dilated split form: one tensor per side, no staging BatchNorm
+    const bool bsum = h.bsum_y != nullptr;
+    if (bsum && (!h.bsum_mean || !h.bsum_invstd || !h.bsum_gamma || !h.bsum_beta || !h.bsum_partials || !h.bsum_max || h.bsum_groups < 1 ||
+                 B % h.bsum_groups || !(h.bsum_slope >= 0.f && h.bsum_slope <= 1.f)))
+        return UAPS_EINVAL;
+    f.ks = ks; f.th = p.th; f.tw = p.tw; f.n = p.bn; f.ck = p.ck; f.dil = p.dil; f.vec = p.vec; f.bn = xf != nullptr;
+    f.up2 = up2; f.Csplit = Csplit; f.Osplit = Osplit;
+    f.parts = ((H + p.th - 1) / p.th) * ((W + p.tw - 1) / p.tw);      // one part per tile of the plan (s32t too: per 8 rows)
+    const unsigned tune = g_conv_tuning;
     const bool wide = p.tw == 32;
-    // a side with <= 4 channels: the exact-N fp32 kernels (no BatchNorm statistics epilogue, one tensor per side)
-    const bool no_small = (g_conv_tuning & UAPS_TUNE_NO_SMALL) != 0;
     // (on 256-wide maps with bounded operands the full-width-row kernel serves <= 4 output channels too: padded to one 16-channel
     // MFMA tile it streams at the HBM rate of a 16 -> 16 layer, which the 16 x 64-tile VALU kernel does not reach)
-    const bool row16 = p.split && conv_mode() == 2 && hints.bound[0] && ks == 3 && p.dil == 1 && W % 256 == 0 && H % 16 == 0 && p.CoutP == 16 &&
-                       Cin > 8 && Cin <= 32 && Cin % 8 == 0 && !y2 && (!x2 || Csplit >= Cin || hints.bound[1]) &&
-                       !(g_conv_tuning & (UAPS_TUNE_NO_ROW16 | UAPS_TUNE_NO_HP16));
-    // BatchNorm-backward sums in the epilogue (uaps_call_hints::bsum_*): ONE kernel, the 16 -> 16 input gradient on a 256-wide map
-    const bool bsum = hints.bsum_y != nullptr;
-    if (bsum) {
-        if (!hints.bsum_mean || !hints.bsum_invstd || !hints.bsum_gamma || !hints.bsum_beta || !hints.bsum_partials || !hints.bsum_max ||
-            hints.bsum_groups < 1 || B % hints.bsum_groups || !(hints.bsum_slope >= 0.f && hints.bsum_slope <= 1.f)) return UAPS_EINVAL;
-        if (!(row16 && !x2 && !xf && !stats && !up2 && Cin == 16 && Cout == 16 && W == 256 && p.vec && (uintptr_t)hints.bsum_y % 16 == 0 &&
-              (uintptr_t)hints.bsum_max % 16 == 0))
-            return UAPS_ENOFORM;
-        a.bs_y = hints.bsum_y; a.bs_mean = hints.bsum_mean; a.bs_invstd = hints.bsum_invstd; a.bs_gamma = hints.bsum_gamma;
-        a.bs_beta = hints.bsum_beta; a.bs_slope = hints.bsum_slope; a.bs_Bg = B / hints.bsum_groups; a.bs_max = hints.bsum_max;
-        a.stats = (float2*)hints.bsum_partials;
-        uaps::account_bytes(4.0 * B * H * W * Cout);      // the BatchNorm's raw input, once more
-    }
-    // the up-sampling form exists in ONE kernel: up4's first convolution on a 256-wide map (16 + 16 -> 16 channels, bounded operands)
-    // (every condition of the branch below that reaches launch_hr16_up is part of this test -- the 32-pixel-wide tile plan, no 32x32 /
-    // GEMM-tiled plan -- so that no other kernel can ever be handed the low-resolution x2 as if it were a full-resolution tensor)
-    if (up2 && !(row16 && wide && !p.s32 && !p.g1 && p.dil == 1 && x2 && Csplit == 16 && Cin == 32 && W == 256 && !xf && p.vec &&
-                 up2_pattern_ok(W / 2)))
-        return UAPS_ENOFORM;
-    if (!no_small && !row16 && p.small && p.vec && !stats && !x2 && !y2 && (p.small == 1 || !xf)) return launch_small(a, p.small, s);
-    if (p.split) {
-        // the split weights follow the exact ones in the packed buffer (uaps_conv_pack_floats)
-        a.wp = wp + (size_t)ks * ks * p.CinP * p.CoutP;
-        a.CinP = split_cgroups(Cin);
-        // mode 2 and every tensor operand bounded: the two-piece fp16 form; its weights follow the bf16 pieces behind a header
-        if (conv_mode() == 2 && hints.bound[0] && (!x2 || Csplit >= Cin || hints.bound[1])) {
-            const size_t piece = (size_t)ks * ks * a.CinP * p.CoutP * 4;
-            a.wscale = a.wp + 3 * piece + 16;         // {s, 1 / s, max|w|} behind the 16 partial maxima
-            a.wp = a.wp + 3 * piece + kH16Header;
-            a.in_bound = hints.bound[0]; a.in_mul = hints.mul[0];
-            if (x2 && Csplit < Cin) { a.in2_bound = hints.bound[1]; a.in2_mul = hints.mul[1]; }
-            a.err = uaps::error_word();
-        }
+    const bool row16 = p.split && conv_mode() == 2 && h.bound[0] && ks == 3 && p.dil == 1 && W % 256 == 0 && H % 16 == 0 && p.CoutP == 16 &&
+                       Cin > 8 && Cin <= 32 && Cin % 8 == 0 && !c.y2 && (!c.x2 || Csplit >= Cin || h.bound[1]) &&
+                       !(tune & (UAPS_TUNE_NO_ROW16 | UAPS_TUNE_NO_HP16));
+    // a side with <= 4 channels: the exact-N fp32 kernels (no BatchNorm statistics epilogue, one tensor per side)
+    if (!(tune & UAPS_TUNE_NO_SMALL) && !row16 && p.small && p.vec && !c.stats && !c.x2 && !c.y2 && (p.small == 1 || !xf)) {
+        f.kind = FwdKind::Small;
+    } else if (p.split) {
+        // mode 2 and every tensor operand bounded: the two-piece fp16 form
+        f.h16 = conv_mode() == 2 && h.bound[0] && (!c.x2 || Csplit >= Cin || h.bound[1]);
+        f.n = p.sbn;
         // the whole-layer-width tile form (conv_split_g.hpp): with statistics only when the caller promised the bounds up front
         // (UAPS_CONV_BOUNDED: the partial-sum layout of this form is what uaps_conv_fwd_stats_parts reported for the same bit)
         // (not with the staging-time BatchNorm: its transform sits exposed in a one-wave-per-SIMD kernel -- 46.7 against 41.1 us of
         // conv_hfwd_bn_kernel -- so such calls keep the tile kernels AND their partial-sum layout: see uaps_conv_fwd_stats_parts)
-        if (p.g128 && xf && stats && p.bounded) return UAPS_EINVAL;      // (the bit changes the statistics layout; this form has none)
-        if (p.g128 && !xf && stats && p.bounded && !a.wscale) return UAPS_EINVAL;
-        if (p.g128 && !xf && a.wscale && (!stats || p.bounded) && (Csplit == Cin || Csplit % 32 == 0) && (Osplit == Cout || Osplit % 128 == 0) &&
-            !hints.out_amax && !bsum && !up2)
-            return launch_hg128(a, s);
-        if (p.g1) {
-            // no two-tensor / BatchNorm-in-staging form of the GEMM-tiled kernels: the 3x3-style tiling (never with statistics, see above)
-            if (!x2 && !y2 && !xf) {
-                const bool wide = a.wscale && p.CoutP % 256 == 0 && !(g_conv_tuning & UAPS_TUNE_G1_NARROW);
-                return launch_g1(a, wide ? 256 : (p.CoutP % 128 == 0 ? 128 : 64), s);
-            }
+        if (p.g128 && !xf && f.h16 && (!c.stats || p.bounded) && (Csplit == Cin || Csplit % 32 == 0) && (Osplit == Cout || Osplit % 128 == 0) &&
+            !h.out_amax && !bsum && !up2) {
+            f.kind = FwdKind::HG128;
+            f.deep = (tune & UAPS_TUNE_G_DEEP) != 0;
+            f.parts = H / 4;
+        } else if (p.g1 && !c.x2 && !c.y2 && !xf) {
+            // (no two-tensor / BatchNorm-in-staging form of the GEMM-tiled kernels: those take the 3x3-style tiling)
+            f.kind = FwdKind::G1;
+            f.parts = (H * W + 127) / 128;
+            f.n = (f.h16 && p.CoutP % 256 == 0 && !(tune & UAPS_TUNE_G1_NARROW)) ? 256 : (p.CoutP % 128 == 0 ? 128 : 64);
+        } else if (f.h16 && ks == 3 && p.dil == 1 && Cin == 16 && Cout == 32 && !c.stats && !xf && !c.x2 && (Osplit == Cout || Osplit == 16) &&
+                   W % 256 == 0 && H % 16 == 0 && !(tune & (UAPS_TUNE_NO_ROW16 | UAPS_TUNE_NO_HP16))) {
+            // 16 -> 32 channels on a 256-wide map without statistics (the input gradient of up4's two-tensor convolution): two output
+            // tiles of the full-width-row kernel, written as one or two 16-channel tensors
+            f.kind = FwdKind::HR16x2;
+            f.strips = W > 256;
+        } else if (p.dil > 1) {
+            f.kind = FwdKind::S32D;
+        } else if (p.s32) {
+            f.kind = p.s32t ? FwdKind::S32T : FwdKind::S32;
+        } else if (!(tune & UAPS_TUNE_NO_HP16) && f.h16 && ks == 3 && wide && p.CoutP == 16 && Cin > 8 && Cin <= 32 && Osplit == Cout) {
+            f.n = Cin <= 16 ? 2 : 4;
+            f.strips = W > 256;
+            // the up-sampling form exists in ONE kernel: up4's first convolution on a 256-wide map (16 + 16 -> 16 channels)
+            if (up2 && row16 && Csplit == 16 && Cin == 32 && W == 256 && up2_pattern_ok(W / 2)) f.kind = FwdKind::HR16Up;
+            // BatchNorm-backward sums in the epilogue: ONE kernel, the 16 -> 16 input gradient on a 256-wide map
+            else if (bsum && row16 && !c.x2 && !xf && !c.stats && !up2 && Cin == 16 && Cout == 16 && W == 256 &&
+                     (uintptr_t)h.bsum_y % 16 == 0 && (uintptr_t)h.bsum_max % 16 == 0) f.kind = FwdKind::HR16Bs;
+            else if (W % 256 == 0 && H % 16 == 0 && !(tune & UAPS_TUNE_NO_ROW16)) f.kind = FwdKind::HR16;
+            else f.kind = FwdKind::HP16;
+        } else {
+            f.kind = FwdKind::Split;
+            f.n = p.sbn == 16 ? 16 : 32;
+            f.ck = ks == 1 ? 32 : (p.sck == 8 ? 8 : 16);
         }
-        // 16 -> 32 channels on a 256-wide map without statistics (the input gradient of up4's two-tensor convolution): two output
-        // tiles of the full-width-row kernel, written as one or two 16-channel tensors
-        if (a.wscale && ks == 3 && p.dil == 1 && Cin == 16 && Cout == 32 && !stats && !xf && !x2 && (Osplit == Cout || Osplit == 16) &&
-            W % 256 == 0 && H % 16 == 0 && !(g_conv_tuning & (UAPS_TUNE_NO_ROW16 | UAPS_TUNE_NO_HP16))) return launch_hr16x2(a, s);
-        if (p.dil > 1) return p.sbn == 64 ? launch_s32d<64>(a, p.dil, s) : launch_s32d<32>(a, p.dil, s);
-        if (p.s32 && p.s32t) return launch_s32t(a, s);
-        if (p.s32) return p.sbn == 64 ? launch_s32<64>(a, s) : launch_s32<32>(a, s);
-        const bool no_hp16 = (g_conv_tuning & UAPS_TUNE_NO_HP16) != 0;
-        if (!no_hp16 && a.wscale && ks == 3 && wide && p.CoutP == 16 && Cin > 8 && Cin <= 32 && Osplit == Cout) {
-            if (up2) return launch_hr16_up(a, s);
-            if (bsum) return launch_hr16_bs(a, s);
-            if (W % 256 == 0 && H % 16 == 0 && !(g_conv_tuning & UAPS_TUNE_NO_ROW16)) return launch_hr16(a, s);
-            return launch_hp16(a, s);
-        }
-        if (up2) return UAPS_ENOFORM;      // (unreachable by the test above; kept so that a future edit of either cannot launch a wrong form)
-        if (ks == 3) return wide ? dispatch_sfwd<3, 8, 32>(a, p.sbn, p.sck, s) : dispatch_sfwd<3, 16, 16>(a, p.sbn, p.sck, s);
-        return wide ? dispatch_sfwd<1, 8, 32>(a, p.sbn, p.sck, s) : dispatch_sfwd<1, 16, 16>(a, p.sbn, p.sck, s);
+    } else {
+        f.kind = FwdKind::Tile;
+        // the staging-time BatchNorm: 16-byte form, 8-channel chunks, no dilation
+        if (xf && (!p.vec || p.ck != 8 || p.dil != 1)) return UAPS_ERANGE;
     }
-    if (up2) return UAPS_ENOFORM;
-    if (p.dil == 2) return dispatch_dilated<2>(a, p.bn, p.vec, p.extra_lds, s);
-    if (p.dil == 4) return dispatch_dilated<4>(a, p.bn, p.vec, p.extra_lds, s);
-    if (ks == 3) return wide ? dispatch_bn_ck<3, 8, 32>(a, p.bn, p.ck, p.vec, p.extra_lds, s) : dispatch_bn_ck<3, 16, 16>(a, p.bn, p.ck, p.vec, p.extra_lds, s);
-    return wide ? dispatch_bn_ck<1, 8, 32>(a, p.bn, p.ck, p.vec, p.extra_lds, s) : dispatch_bn_ck<1, 16, 16>(a, p.bn, p.ck, p.vec, p.extra_lds, s);
+    // launch geometry
+    long n = 0;
+    f.block = kConvThreads;
+    switch (f.kind) {
+    case FwdKind::Tile: case FwdKind::Split: case FwdKind::S32: case FwdKind::S32T: case FwdKind::S32D:
+        if (f.kind == FwdKind::S32 || f.kind == FwdKind::S32D) { f.th = 8; f.tw = 32; }
+        if (f.kind == FwdKind::S32T) { f.th = 16; f.tw = 32; f.n = 32; }
+        f.tiles_x = (W + f.tw - 1) / f.tw; f.tiles_y = (H + f.th - 1) / f.th; f.nblk = p.CoutP / f.n;
+        n = (long)B * f.tiles_x * f.tiles_y * f.nblk;
+        if (f.kind == FwdKind::Tile) f.lds = p.extra_lds;     // unused dynamic LDS, requested only to cap the co-resident workgroups per CU
+        f.th = p.th; f.tw = p.tw;                             // (the names carry the plan's tile)
+        break;
+    case FwdKind::G1:
+        f.tiles_x = (H * W + 127) / 128; f.tiles_y = 1; f.nblk = p.CoutP / f.n;
+        n = (long)B * f.tiles_x * f.nblk;
+        break;
+    case FwdKind::HG128:
+        f.tiles_x = 1; f.tiles_y = H / 4; f.nblk = Cout / 128;
+        n = (long)B * f.tiles_y * f.nblk;
+        f.block = kHg128Threads; f.lds = kHg128Lds;
+        break;
+    case FwdKind::Small:
+        f.tiles_x = (W + 63) / 64; f.tiles_y = (H + 15) / 16; f.nblk = 1;
+        n = (long)B * f.tiles_x * f.tiles_y;
+        break;
+    case FwdKind::HP16: {
+        f.tiles_x = (W + 31) / 32; f.tiles_y = (H + 7) / 8; f.nblk = 1;
+        const long ntiles = (long)B * f.tiles_x * f.tiles_y;
+        if (ntiles <= 0 || ntiles > 0x7fffffffL) return UAPS_EINVAL;
+        // one resident round: 3 (16 input channels) or 2 (32) workgroups fit a CU (registers), 256 CUs; forcing 4 spills and is slower
+        const long want = Cin <= 16 ? 768 : 512;
+        f.grid = grid8(ntiles < want ? ntiles : want);
+        return *out = f, UAPS_OK;
+    }
+    case FwdKind::HR16: case FwdKind::HR16Up: case FwdKind::HR16Bs: case FwdKind::HR16x2: {
+        // runs of 16 rows of one 256-wide column strip; HR16: 2 workgroups of 256 threads per CU for 16 input channels, 1 workgroup of
+        // 512 threads (135 KB of LDS) for 32
+        const long nruns = (long)B * (H / 16) * (f.kind == FwdKind::HR16 || f.kind == FwdKind::HR16x2 ? W / 256 : 1);
+        if (nruns <= 0 || nruns > 0x7fffffffL) return UAPS_EINVAL;
+        const long want = f.kind == FwdKind::HR16Up ? 256 : (f.kind == FwdKind::HR16 && Cin > 16) ? 256 : 512;
+        f.grid = grid8(nruns < want ? nruns : want);
+        f.block = (f.kind == FwdKind::HR16Up || (f.kind == FwdKind::HR16 && Cin > 16)) ? 512 : 256;
+        return *out = f, UAPS_OK;
+    }
+    }
+    if (n <= 0 || (n + 7) / 8 * 8 > 0x7fffffffL) return UAPS_EINVAL;
+    f.grid = grid8(n);
+    *out = f;
+    return UAPS_OK;
 }
 
+// The call's optional requests against its resolved form (nothing is launched when one fails)
+int check_fwd(const uaps_call_hints& h, const FwdCall& c, const FwdForm& f) {
+    const FwdPlan& p = f.plan;
+    // UAPS_CONV_BOUNDED on a shape of the whole-layer-width form: the caller promised bounds for every operand, and the staging-time
+    // BatchNorm has no such form (the bit changes the statistics layout)
+    if (split_form(f.kind) && p.g128 && p.bounded && c.stats && (c.xf || !f.h16)) return UAPS_EINVAL;
+    // the partials must come in the layout uaps_conv_fwd_stats_parts reported for the shape and cfg (the Python layer hands a call
+    // that cannot run the GEMM-tiled plan cfg bit 28: conv.plan_cfg)
+    int parts = 0;
+    if (c.stats && (stats_parts(c.B, c.Cin, c.Cout, c.H, c.W, c.ks, c.cfg & ~UAPS_CONV_X2_UP2, &parts) || parts != f.parts)) return UAPS_ERANGE;
+    // out_amax: raised to max|y| by the fp32-instruction kernels only (the U-Net's 1x1 projections, whose output has no BatchNorm
+    // behind it to bound it)
+    if (h.out_amax && (f.kind != FwdKind::Tile || p.small || p.g1 || (uintptr_t)h.out_amax % 16)) return UAPS_ENOFORM;
+    if (h.bsum_y && f.kind != FwdKind::HR16Bs) return UAPS_ENOFORM;
+    if (f.up2 && f.kind != FwdKind::HR16Up) return UAPS_ENOFORM;
+    return UAPS_OK;
+}
+
+// ---- the launch: a switch on the form (no choice is made below; the form names one instantiation) ----
+using FwdKernel = void (*)(ConvFwdArgs);
+
+template <int KS, int TH, int TW, int BN, int CK, int DIL>
+FwdKernel tile_kernel(const FwdForm& f) {
+    if constexpr (DIL == 1 && CK == 8) {
+        if (f.bn) return conv_fwd_bn_kernel<KS, TH, TW, BN, CK, 4, 1>;
+    }
+    return f.vec ? conv_fwd_kernel<KS, TH, TW, BN, CK, 4, DIL> : conv_fwd_kernel<KS, TH, TW, BN, CK, 1, DIL>;
+}
+template <int KS, int TH, int TW, int DIL>
+FwdKernel tile_kernel_n(const FwdForm& f) {
+    if constexpr (KS == 3 && DIL == 1) {
+        if (f.ck == 4) return tile_kernel<KS, TH, TW, 16, 4, 1>(f);
+    }
+    return f.n == 16 ? tile_kernel<KS, TH, TW, 16, 8, DIL>(f) : f.n == 32 ? tile_kernel<KS, TH, TW, 32, 8, DIL>(f) : tile_kernel<KS, TH, TW, 64, 8, DIL>(f);
+}
+
+template <int KS, int TH, int TW, int BN, int CK>
+FwdKernel split_kernel(const FwdForm& f) {
+    if (f.h16) return f.bn ? conv_hfwd_bn_kernel<KS, TH, TW, BN, CK> : conv_hfwd_kernel<KS, TH, TW, BN, CK>;
+    return f.bn ? conv_sfwd_bn_kernel<KS, TH, TW, BN, CK> : conv_sfwd_kernel<KS, TH, TW, BN, CK>;
+}
+template <int KS, int TH, int TW>
+FwdKernel split_kernel_n(const FwdForm& f) {
+    if constexpr (KS == 3) {
+        if (f.ck == 8) return f.n == 16 ? split_kernel<3, TH, TW, 16, 8>(f) : split_kernel<3, TH, TW, 32, 8>(f);
+        return f.n == 16 ? split_kernel<3, TH, TW, 16, 16>(f) : split_kernel<3, TH, TW, 32, 16>(f);
+    } else {
+        return f.n == 16 ? split_kernel<1, TH, TW, 16, 32>(f) : split_kernel<1, TH, TW, 32, 32>(f);
+    }
+}
+
+template <int BN>
+FwdKernel s32_kernel(const FwdForm& f) {
+    if (f.h16) return f.bn ? conv_h32_bn_kernel<BN> : conv_h32_kernel<BN>;
+    return f.bn ? conv_s32_bn_kernel<BN> : conv_s32_kernel<BN>;
+}
+template <int BN>
+FwdKernel s32d_kernel(const FwdForm& f) {
+    if (f.h16) return f.dil == 2 ? conv_h32d_kernel<BN, 2> : conv_h32d_kernel<BN, 4>;
+    return f.dil == 2 ? conv_s32d_kernel<BN, 2> : conv_s32d_kernel<BN, 4>;
+}
+template <int N>
+FwdKernel row16_kernel(const FwdForm& f) {
+    if (f.kind == FwdKind::HP16) return f.bn ? conv_hp16_bn_kernel<N> : conv_hp16_kernel<N>;
+    if (f.strips) return f.bn ? conv_hr16w_bn_kernel<N> : conv_hr16w_kernel<N>;
+    return f.bn ? conv_hr16_bn_kernel<N> : conv_hr16_kernel<N>;
+}
+
+FwdKernel fwd_kernel(const FwdForm& f) {
+    switch (f.kind) {
+    case FwdKind::Tile:
+        if (f.dil > 1) return f.dil == 2 ? tile_kernel_n<3, 8, 32, 2>(f) : tile_kernel_n<3, 8, 32, 4>(f);
+        if (f.ks == 3) return f.tw == 32 ? tile_kernel_n<3, 8, 32, 1>(f) : tile_kernel_n<3, 16, 16, 1>(f);
+        return f.tw == 32 ? tile_kernel_n<1, 8, 32, 1>(f) : tile_kernel_n<1, 16, 16, 1>(f);
+    case FwdKind::Small: return f.bn ? conv_small_bn_kernel<8, 4> : conv_small_kernel<8, 4>;
+    case FwdKind::Split:
+        if (f.ks == 3) return f.tw == 32 ? split_kernel_n<3, 8, 32>(f) : split_kernel_n<3, 16, 16>(f);
+        return f.tw == 32 ? split_kernel_n<1, 8, 32>(f) : split_kernel_n<1, 16, 16>(f);
+    case FwdKind::S32: return f.n == 64 ? s32_kernel<64>(f) : s32_kernel<32>(f);
+    case FwdKind::S32T:
+        if (f.h16) return f.bn ? conv_h32t_bn_kernel<32> : conv_h32t_kernel<32>;
+        return f.bn ? conv_s32t_bn_kernel<32> : conv_s32t_kernel<32>;
+    case FwdKind::S32D: return f.n == 64 ? s32d_kernel<64>(f) : s32d_kernel<32>(f);
+    case FwdKind::G1:
+        if (!f.h16) return f.n == 128 ? conv_g1s_kernel<128> : conv_g1s_kernel<64>;
+        return f.n == 256 ? conv_g1h256_kernel : f.n == 128 ? conv_g1h_kernel<128> : conv_g1h_kernel<64>;
+    case FwdKind::HG128: return f.bn ? conv_hg128_bn_kernel : f.deep ? conv_hg128_deep_kernel : conv_hg128_kernel;
+    case FwdKind::HP16: case FwdKind::HR16: return f.n == 2 ? row16_kernel<2>(f) : row16_kernel<4>(f);
+    case FwdKind::HR16Up: return conv_hr16_up_kernel;
+    case FwdKind::HR16Bs: return conv_hr16_bs_kernel;
+    case FwdKind::HR16x2: return f.strips ? conv_hr16wx2_kernel : conv_hr16x2_kernel;
+    }
+    return nullptr;
+}
+
+int launch_fwd(const uaps_call_hints& h, const FwdCall& c, const FwdForm& f, hipStream_t s) {
+    const FwdPlan& p = f.plan;
+    const int ks = c.ks, Cin = c.Cin;
+    ConvFwdArgs a{};
+    a.in = c.x; a.in2 = c.x2; a.Csplit = f.Csplit; a.out2 = c.y2; a.Osplit = f.Osplit;
+    a.wp = c.wp; a.bias = c.bias; a.out = c.y; a.stats = (float2*)c.stats;
+    if (c.stats) { a.stats_mean = h.stats_mean; a.stats_bias = h.stats_bias; }
+    a.B = c.B; a.Cin = Cin; a.Cout = c.Cout; a.H = c.H; a.W = c.W;
+    a.CinP = p.CinP; a.CoutP = p.CoutP;
+    a.xf = (const float2*)c.xf; a.xf_slope = c.xf_slope; a.xf_Bg = c.xf ? c.B / c.groups : c.B;
+    a.amax = h.out_amax;
+    a.tiles_x = f.tiles_x; a.tiles_y = f.tiles_y; a.nblk = f.nblk;
+    if (split_form(f.kind)) {
+        // the split weights follow the exact ones in the packed buffer (uaps_conv_pack_floats)
+        a.wp = c.wp + (size_t)ks * ks * p.CinP * p.CoutP;
+        a.CinP = split_cgroups(Cin);
+        if (f.h16) {                                  // the fp16 pieces follow the bf16 ones behind a header
+            const size_t piece = (size_t)ks * ks * a.CinP * p.CoutP * 4;
+            a.wscale = a.wp + 3 * piece + 16;         // {s, 1 / s, max|w|} behind the 16 partial maxima
+            a.wp = a.wp + 3 * piece + kH16Header;
+            a.in_bound = h.bound[0]; a.in_mul = h.mul[0];
+            if (c.x2 && f.Csplit < Cin) { a.in2_bound = h.bound[1]; a.in2_mul = h.mul[1]; }
+            a.err = uaps::error_word();
+        }
+    }
+    if (f.kind == FwdKind::HG128) {
+        static bool attr = false;
+        if (!attr) {                                  // (idempotent; > 48 KB of dynamic LDS needs the attribute once per kernel)
+            (void)hipFuncSetAttribute((const void*)conv_hg128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kHg128Lds);
+            (void)hipFuncSetAttribute((const void*)conv_hg128_bn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kHg128Lds);
+            (void)hipFuncSetAttribute((const void*)conv_hg128_deep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kHg128Lds);
+            attr = true;
+        }
+    } else if (f.kind == FwdKind::HR16Up) {
+        a.up_rh = (float)(c.H / 2 - 1) / (float)(c.H - 1); a.up_rw = (float)(c.W / 2 - 1) / (float)(c.W - 1);      // as uaps_up_cat_fwd
+    } else if (f.kind == FwdKind::HR16Bs) {
+        a.bs_y = h.bsum_y; a.bs_mean = h.bsum_mean; a.bs_invstd = h.bsum_invstd; a.bs_gamma = h.bsum_gamma;
+        a.bs_beta = h.bsum_beta; a.bs_slope = h.bsum_slope; a.bs_Bg = c.B / h.bsum_groups; a.bs_max = h.bsum_max;
+        a.stats = (float2*)h.bsum_partials;
+        uaps::account_bytes(4.0 * c.B * c.H * c.W * c.Cout);      // the BatchNorm's raw input, once more
+    }
+    UAPS_LAUNCH_MAIN(fwd_kernel(f), dim3(f.grid), dim3(f.block), f.lds, s, a);
+    return (int)hipGetLastError();
+}
+
+// the rocprofv3 name of a form's kernel (without namespace)
+void fwd_form_name(const FwdForm& f, char* buf, size_t len) {
+    const char* bn = f.bn ? "_bn" : "";
+    const char hs = f.h16 ? 'h' : 's';
+    switch (f.kind) {
+    case FwdKind::Tile: snprintf(buf, len, "conv_fwd%s_kernel<%d, %d, %d, %d, %d, %d, %d>", bn, f.ks, f.th, f.tw, f.n, f.ck, f.vec ? 4 : 1, f.dil); break;
+    case FwdKind::Small: snprintf(buf, len, "conv_small%s_kernel<8, 4>", bn); break;
+    case FwdKind::Split: snprintf(buf, len, "conv_%cfwd%s_kernel<%d, %d, %d, %d, %d>", hs, bn, f.ks, f.th, f.tw, f.n, f.ck); break;
+    case FwdKind::S32: snprintf(buf, len, "conv_%c32%s_kernel<%d>", hs, bn, f.n); break;
+    case FwdKind::S32T: snprintf(buf, len, "conv_%c32t%s_kernel<32>", hs, bn); break;
+    case FwdKind::S32D: snprintf(buf, len, "conv_%c32d_kernel<%d, %d>", hs, f.n, f.dil); break;
+    case FwdKind::G1:
+        if (f.h16 && f.n == 256) snprintf(buf, len, "conv_g1h256_kernel");
+        else snprintf(buf, len, "conv_g1%c_kernel<%d>", hs, f.n);
+        break;
+    case FwdKind::HG128: snprintf(buf, len, "conv_hg128%s_kernel", f.bn ? "_bn" : f.deep ? "_deep" : ""); break;
+    case FwdKind::HP16: snprintf(buf, len, "conv_hp16%s_kernel<%d>", bn, f.n); break;
+    case FwdKind::HR16: snprintf(buf, len, "conv_hr16%s%s_kernel<%d>", f.strips ? "w" : "", bn, f.n); break;
+    case FwdKind::HR16Up: snprintf(buf, len, "conv_hr16_up_kernel"); break;
+    case FwdKind::HR16Bs: snprintf(buf, len, "conv_hr16_bs_kernel"); break;
+    case FwdKind::HR16x2: snprintf(buf, len, "conv_hr16%sx2_kernel", f.strips ? "w" : ""); break;
+    }
+}
+
+}  // namespace
+
+int uaps::conv_fwd_run(const uaps_call_hints& h, const FwdCall& c, uaps_stream_t stream) {
+    if (!c.x || !c.wp || !c.y) return UAPS_EINVAL;
+    FwdForm f;
+    int rc = resolve_fwd(h, c, &f);
+    if (rc) return rc;
+    // every input and output element once
+    uaps::account_bytes(4.0 * c.B * c.H * c.W * ((double)f.Csplit + (c.Cin - f.Csplit) * (f.up2 ? 0.25 : 1.0) + c.Cout));
+    rc = check_fwd(h, c, f);
+    if (rc) return rc;
+    return launch_fwd(h, c, f, (hipStream_t)stream);
+}
+
+int uaps::conv_fwd_name(const uaps_call_hints& h, const FwdCall& c, char* buf, size_t buflen) {
+    FwdForm f;
+    int rc = resolve_fwd(h, c, &f);
+    if (!rc) rc = check_fwd(h, c, f);
+    if (rc) return rc;
+    if (!buf || buflen < 64) return UAPS_EINVAL;
+    fwd_form_name(f, buf, buflen);
+    return UAPS_OK;
+}
+
+namespace {
+// the entry points below hand their arguments on as one FwdCall
+int conv_fwd_any(const uaps_call_hints& h, const float* x, const float* wp, const float* bias, float* y, int B, int Cin, int Cout, int H, int W, int ks,
+                 int cfg, hipStream_t s, float2* stats = nullptr, const float* x2 = nullptr, int Csplit = -1,
+                 float* y2 = nullptr, int Osplit = -1, const void* xf = nullptr, float xf_slope = 0.f, int groups = 1) {
+    const FwdCall c{x, wp, bias, y, B, Cin, Cout, H, W, ks, cfg, stats, x2, Csplit, y2, Osplit, xf, xf_slope, groups};
+    return uaps::conv_fwd_run(h, c, s);
+}
 }  // namespace
 
 static PackDesc make_pack_desc(const float* w, float* wf, float* wb, int Cout, int Cin, int ks) {
@@ -602,12 +615,11 @@ extern "C" int uaps_conv_fwd_bn(const float* x_raw, const void* xf, float slope,
 }
 
 extern "C" int uaps_conv_fwd_stats_parts(int B, int Cin, int Cout, int H, int W, int ks, int cfg, int* parts_per_image) {
-    FwdPlan p{};
-    const int rc = plan_fwd(nullptr, nullptr, B, Cin, Cout, H, W, ks, cfg, &p);
+    int parts = 0;
+    const int rc = stats_parts(B, Cin, Cout, H, W, ks, cfg, &parts);
     if (rc) return rc;
     if (!parts_per_image) return UAPS_EINVAL;
-    *parts_per_image = p.g1 ? (H * W + 127) / 128 : ((H + p.th - 1) / p.th) * ((W + p.tw - 1) / p.tw);
-    if (p.g128 && p.bounded) *parts_per_image = H / 4;      // conv_split_g.hpp: one part per 4-row band
+    *parts_per_image = parts;
     return UAPS_OK;
 }
 
@@ -652,19 +664,10 @@ extern "C" int uaps_conv_bwd_data(const float* dy, const float* wb, float* dx, i
     return conv_fwd_any(take_hints(), dy, wb, nullptr, dx, B, Cout, Cin, H, W, ks, cfg, (hipStream_t)stream);
 }
 
-// Name of the kernel instantiation uaps_conv_fwd / uaps_conv_bwd_data launch for these dimensions, as
-// rocprofv3 prints it (bench.py groups its HIP-event timings by it).  For bwd_data pass (Cout, Cin) swapped.
+// Name of the kernel instantiation uaps_conv_fwd / uaps_conv_bwd_data launch for these dimensions (aligned tensors, no hints), as
+// rocprofv3 prints it.  For bwd_data pass (Cout, Cin) swapped.  uaps_conv_ex_variant names the kernel of a whole call.
 extern "C" int uaps_conv_fwd_variant(int B, int Cin, int Cout, int H, int W, int ks, int cfg, char* buf, size_t buflen) {
-    FwdPlan p{};
-    const int rc = plan_fwd(nullptr, nullptr, B, Cin, Cout, H, W, ks, cfg, &p);
-    if (rc) return rc;
-    if (!buf || buflen < 64) return UAPS_EINVAL;
-    if (p.small) snprintf(buf, buflen, "conv_small_kernel<8, 4>");
-    else if (p.g1) snprintf(buf, buflen, "conv_g1s_kernel<%d>", p.CoutP % 128 == 0 ? 128 : 64);
-    else if (p.s32 && p.dil > 1) snprintf(buf, buflen, "conv_s32d_kernel<%d, %d>", p.sbn, p.dil);
-    else if (p.s32 && p.s32t) snprintf(buf, buflen, "conv_s32t_kernel<32>");
-    else if (p.s32) snprintf(buf, buflen, "conv_s32_kernel<%d>", p.sbn);
-    else if (p.split) snprintf(buf, buflen, "conv_sfwd_kernel<%d, %d, %d, %d, %d>", ks, p.th, p.tw, p.sbn, p.sck);
-    else snprintf(buf, buflen, "conv_fwd_kernel<%d, %d, %d, %d, %d, %d, %d>", ks, p.th, p.tw, p.bn, p.ck, p.vec ? 4 : 1, p.dil);
-    return UAPS_OK;
+    const uaps_call_hints none{};
+    const FwdCall c{nullptr, nullptr, nullptr, nullptr, B, Cin, Cout, H, W, ks, cfg};
+    return conv_fwd_name(none, c, buf, buflen);
 }

@@ -285,15 +285,13 @@ class _BnActConv(torch.autograd.Function):
             _lib.check(rc, "uaps_bn_finalize_train")
             am = _conv._claim_amax(dev)               # conv.request_out_amax(): track max|z| (the 1x1 projection in front of an up-sampling)
             for attempt in range(2):
-                with _conv._timed("fwd_bn", B, Cin, Cout, H, W, ks, fcfg, _conv._h16(xb), want_stats) as tm:
-                    hh = None
-                    if xb is not None or (want_stats and stat_shift is not None) or am is not None:
-                        hh = _lib.mk_hints((xb,) if xb is not None else (), am, stat_shift if want_stats else None)
+                hh = None
+                if xb is not None or (want_stats and stat_shift is not None) or am is not None:
+                    hh = _lib.mk_hints((xb,) if xb is not None else (), am, stat_shift if want_stats else None)
+                with _conv._timed(_conv.FWD, B, Cin, Cout, H, W, ks, fcfg, hh, x=y, y=z, stats=zstats, xf=xf, xf_slope=float(slope), xf_groups=groups):
                     rc = L.uaps_conv_fwd_bn_h(hh, y.data_ptr(), xf.data_ptr(), float(slope), groups, wf.data_ptr(),
                                             bias.data_ptr() if bias is not None else None, z.data_ptr(),
                                             zstats.data_ptr() if want_stats else None, B, Cin, Cout, H, W, ks, fcfg, st)
-                    if rc == _conv.ENOFORM:
-                        tm.on = False
                 if rc != _conv.ENOFORM or am is None:
                     break
                 am = None                             # this layer's kernel cannot track it: run without (the caller falls back)
@@ -338,16 +336,14 @@ class _BnActConv(torch.autograd.Function):
             out = torch.empty_like(dz) if lz is not None else None
             with _lib.device_guard(dev):
                 st = _lib.current_stream(dev)
-                with _conv._timed("wrw_bn", B, Cc, Cout, H, W, ks, cfg, _conv._h16(dzb, xb), dt=lz is not None) as tm:
-                    hh = None
-                    if lz is not None:
-                        hh = _lib.mk_hints((dzb, xb), dyt=(lz.y, lz.coef, out, lz.slope, lz.groups))
-                    elif dzb is not None and xb is not None:
-                        hh = _lib.mk_hints((dzb, xb))
+                hh = None
+                if lz is not None:
+                    hh = _lib.mk_hints((dzb, xb), dyt=(lz.y, lz.coef, out, lz.slope, lz.groups))
+                elif dzb is not None and xb is not None:
+                    hh = _lib.mk_hints((dzb, xb))
+                with _conv._timed(_conv.WRW, B, Cc, Cout, H, W, ks, cfg, hh, y_grad=dz, x=y, xf=xf, xf_slope=slope, xf_groups=groups):
                     rc = L.uaps_conv_bwd_weight_partial_bn_h(hh, dz.data_ptr(), y.data_ptr(), xf.data_ptr(), slope, groups, int(want_db), B, Cc,
                                                            Cout, H, W, ks, cfg, cws.data_ptr(), cws.numel(), st)
-                    if lz is not None and rc == lazybn.ENOFORM:
-                        tm.on = False
                 if lz is not None and rc == lazybn.ENOFORM:
                     return None
                 _lib.check(rc, "uaps_conv_bwd_weight_partial_bn")

@@ -4,10 +4,17 @@ unlabelled, NEU-Seg-shaped 256x256 4-class, K=3 auxiliary decoders = 4 heads).
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
   python bench.py ... --dump-outputs DIR                 (also writes what the last timed step computed: dump_outputs)
+  python bench.py ... --full                             (also every side measurement, see below)
 
 A step = UAPSTrainer.train_step on one synthetic batch pair resident in HBM (16 labelled + 16
 unlabelled images per GPU, config[1] of BASELINE.json): two forwards, fused HIP loss block, backward,
 RCCL gradient average (N>1), Adam.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, runs the W warm-up and K timed steps, writes --dump-outputs and prints the headline line.  --full adds,
+after the timed steps: clock / power sampling, the single-stream per-kernel analysis pass and the roofline built from it, the
+fp32-MFMA and exact-bf16x3 legs, the gradient-exchange figures (N>1), BASELINE.json's other configurations, the inference block
+and the CPU baseline.  --analysis-steps, --exact-steps, --other-configs and the --no-* options tune those legs and do nothing
+without --full.
 """
 import argparse
 import json
@@ -428,6 +435,10 @@ def main():
     ap.add_argument("--aux", type=int, default=3)
     ap.add_argument("--in-chns", type=int, default=3, help="image channels (1 for the DAGM-shaped configs[3])")
     ap.add_argument("--net", default="unet_uaps", help="unet_uaps (BASELINE.json configs[1], the reported metric) or resnet50_uaps (configs[4] shape study)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every side measurement (power log, analysis pass and roofline, strict-arithmetic "
+                         "legs, exchange figures, other configs, inference block, CPU baseline), tuned by --analysis-steps, --exact-steps, "
+                         "--other-configs, --no-inference, --no-power-log and --no-cpu-baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--single-stream", action="store_true",
                     help="time the headline steps with all launches on one HIP stream (default: one stream per auxiliary decoder, "
@@ -451,8 +462,8 @@ def main():
         # not under a launcher: this process becomes one (it has touched no GPU and imports no torch) and exits with the job's code
         raise SystemExit(spawn_ranks(args.gpus))
 
-    # rank 0 samples clock and socket power for the whole run: the child process starts before anything here touches the GPU
-    plog = PowerLog(0.01) if int(os.environ.get("RANK", "0")) == 0 and not args.no_power_log else None
+    # --full: rank 0 samples clock and socket power for the whole run: the child process starts before anything here touches the GPU
+    plog = PowerLog(0.01) if args.full and int(os.environ.get("RANK", "0")) == 0 and not args.no_power_log else None
 
     import numpy as np
     import torch
@@ -583,7 +594,7 @@ def main():
     # instantiation and sums the step's algorithmic flops), then `analysis_steps` steps with events around the dominant
     # kernel's launches and the loss kernels only, timed as a whole for the single-stream ms/step ----
     discover, ev, cev, single_ms, alg_bytes = None, {}, {}, None, None
-    if args.analysis_steps > 0:                              # every rank steps (the gradient exchange is collective); rank 0's events are reported
+    if args.full and args.analysis_steps > 0:                # every rank steps (the gradient exchange is collective); rank 0's events are reported
         _unet._DECODER_STREAMS = False
         trainer.step_graph, trainer.optimizer.from_step_state = None, False     # eager launches: events can bracket each kernel
         trainer.train_step(*data.next())                   # re-warm in the new mode
@@ -638,7 +649,7 @@ def main():
 
     exact_ms = split_ms = nocomm_ms = eager_ms = None
     comm = None
-    if args.exact_steps > 0:
+    if args.full and args.exact_steps > 0:
         prev_mode = conv.get_mode()
         trainer.step_graph, trainer.optimizer.from_step_state = None, False
         if world > 1 and trainer.buckets is not None:
@@ -835,8 +846,9 @@ def main():
                           "launch_mode": mode,
                           # every UAPS_* switch whose value is not the package default (uaps_amd/config.py) -- {} = the shipped configuration;
                           # UAPS_DECODER_STREAMS is set by this script itself for the headline (--single-stream turns it off)
-                          "switches": uaps_amd.config.non_default()},
-               "roofline": roof, "kernels": kern}
+                          "switches": uaps_amd.config.non_default()}}
+        if args.full:                                # a plain run has no analysis pass: nothing to report here
+            res.update(roofline=roof, kernels=kern)
         # clock and socket power across the timed region and the analysis pass (tools/power_sampler.py)
         power = None
         if plog is not None:
@@ -893,15 +905,15 @@ def main():
             res["comm"] = comm
         if args.net != "unet_uaps":
             res["config"]["workload"] = f"{args.net} K={args.aux}, {H}x{W} {C}-class, batch {b}+{b} per GPU (not the BASELINE metric config)"
-        if world == 1 and args.other_configs > 0 and args.net == "unet_uaps" and (b, H, C, args.aux) == (16, 256, 4, 3):
+        if args.full and world == 1 and args.other_configs > 0 and args.net == "unet_uaps" and (b, H, C, args.aux) == (16, 256, 4, 3):
             # the other single-GPU shapes of BASELINE.json, a few eager steps each (decoder streams as in the headline): not the
             # metric, but a number the driver sees for them
             res["other_configs"] = other_configs(args.other_configs, dev)
-        if world == 1 and not args.no_inference and args.net == "unet_uaps" and (H, C, args.aux) == (256, 4, 3):
+        if args.full and world == 1 and not args.no_inference and args.net == "unet_uaps" and (H, C, args.aux) == (256, 4, 3):
             res["inference"] = inference_block(dev, H, C, args.aux)
         if world > 1:
             res["config"]["cores_per_rank"] = cores_per_rank
-        if world == 1 and not args.no_cpu_baseline and args.net == "unet_uaps":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.net == "unet_uaps":
             res["cpu_baseline"] = cpu_baseline(b, H, W)
         print(json.dumps(res), flush=True)
     if distributed:

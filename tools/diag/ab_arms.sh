@@ -6,7 +6,7 @@ N=$1; shift
 for rep in $(seq $N); do
   for arm in "$@"; do
     ( [ -n "$arm" ] && export $arm
-      timeout 900 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --exact-steps 0 --other-configs 0 --no-inference --no-power-log 2>/dev/null | python -c "
+      timeout 900 python bench.py --steps 40 --warmup 5 --full --no-cpu-baseline --exact-steps 0 --other-configs 0 --no-inference --no-power-log 2>/dev/null | python -c "
 import json,sys,re,os
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 pat=re.compile(os.environ.get('AB_KERNELS','hwrw|wrw_reduce'))

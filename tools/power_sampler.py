@@ -3,7 +3,7 @@
 
     python tools/power_sampler.py OUT.jsonl [period_s]
 
-bench.py starts this as a CHILD PROCESS before it touches the GPU (the sampler itself never makes a HIP call: it reads the
+bench.py --full starts this as a CHILD PROCESS before it touches the GPU (the sampler itself never makes a HIP call: it reads the
 driver's metrics table through amdsmi, or the hwmon files when amdsmi is not importable) and stops it by closing its stdin.
 One JSON object per line: {"t": unix seconds, "gpus": [{"bdf", "sclk_mhz" (mean over the XCDs' current_gfxclks), "sclk_min_mhz",
 "power_w", "ppt_acc" (PPT-limiter residency accumulator), "acc" (the accumulators' tick counter), "energy" (energy accumulator)}]}.

@@ -20,13 +20,19 @@ def _ref_bn_act(y, bias, bn, slope, train):
 @pytest.mark.parametrize("shape", [(4, 16, 64, 64), (3, 5, 7, 9), (2, 64, 16, 16), (16, 16, 256, 256), (2, 256, 2, 2)])
 def test_bn_act_train_vs_torch(shape):
     from uaps_amd import fused
+    import bn_ref as R
     torch.manual_seed(1)
     B, C, H, W = shape
-    y = (torch.randn(shape, device=DEV) * 1.7 + 0.3).requires_grad_(True)
     bias = torch.randn(C, device=DEV).requires_grad_(True)
     bn = nn.BatchNorm2d(C).to(DEV)
     with torch.no_grad():
         bn.weight.uniform_(0.5, 1.5); bn.bias.normal_(); bn.running_mean.normal_(); bn.running_var.uniform_(0.5, 2)
+    # no pixel near the LeakyReLU kink (|z| >= 5e-4): every pixel and channel is compared below
+    y_np, beta_np = R.kinkfree(np.random.default_rng(1), B, C, H, W, 1, bn.weight.detach().cpu().numpy(), bn.bias.detach().cpu().numpy(),
+                               np.full(C, 0.3), np.full(C, 1.7))
+    with torch.no_grad():
+        bn.bias.copy_(torch.from_numpy(beta_np.astype(np.float32)))
+    y = torch.from_numpy(y_np).to(DEV).requires_grad_(True)
     bn_ref = nn.BatchNorm2d(C).to(DEV); bn_ref.load_state_dict(bn.state_dict())
     out = fused.bn_act(y, bias, bn, 0.01, 0.0, True)
     yr = y.detach().clone().requires_grad_(True); br = bias.detach().clone().requires_grad_(True)
@@ -39,12 +45,12 @@ def test_bn_act_train_vs_torch(shape):
     g = torch.randn_like(out)
     out.backward(g); ref.backward(g)
     scale = float(yr.grad.abs().max())
-    # at the LeakyReLU kink (|z| ~ 1 ulp) the slope choice may legitimately differ: exclude those pixels
+    # at the LeakyReLU kink (|z| ~ 1 ulp) the slope choice may legitimately differ: the inputs hold no such pixel
     z = F.batch_norm(yr.detach() + br.detach().view(1, -1, 1, 1), None, None, bn_ref.weight, bn_ref.bias, training=True, eps=bn.eps)
     ok = z.abs() > 1e-5
     assert float((~ok).float().mean()) < 1e-4
     chan_ok = ok.all(dim=3).all(dim=2).all(dim=0)          # channels without a kink pixel
-    ok = ok & chan_ok.view(1, -1, 1, 1)
+    assert chan_ok.all() and ok.all()
     torch.testing.assert_close(y.grad[ok], yr.grad[ok], rtol=1e-3, atol=2e-5 * scale)
     torch.testing.assert_close(bn.weight.grad[chan_ok], bn_ref.weight.grad[chan_ok], rtol=1e-4, atol=1e-4 * float(bn_ref.weight.grad.abs().max()))
     torch.testing.assert_close(bn.bias.grad[chan_ok], bn_ref.bias.grad[chan_ok], rtol=1e-4, atol=1e-4 * float(bn_ref.bias.grad.abs().max()))

@@ -542,6 +542,8 @@ static int bn_fwd_train_impl(const uaps_call_hints& hints, const float2* given_p
     if (rc) return rc;
     if (!gamma || !beta || !save_mean || !save_invstd || !ws || !(drop_p >= 0.f && drop_p < 1.f)) return UAPS_EINVAL;
     if (groups < 1 || groups > kMaxGroups || B % groups) return UAPS_EINVAL;
+    const float* res = hints.residual;
+    if (res && (drop_p > 0.f || !al16(res))) return UAPS_EINVAL;      // the join has no dropout; the residual is a tensor like y
     // y read and the activated tensor written (+ the residual read; + one more read of y when the statistics pass runs here)
     uaps::account_bytes(4.0 * B * C * H * W * (2.0 + (given_partials ? 0.0 : 1.0) + (hints.residual ? 1.0 : 0.0)));
     const long HW = (long)H * W;
@@ -559,8 +561,6 @@ static int bn_fwd_train_impl(const uaps_call_hints& hints, const float2* given_p
                        given_partials ? given_parts_per_image : nch, (double)HW, conv_bias, gamma, beta, running_mean,
                        running_var, num_batches_tracked, momentum, eps, save_mean, save_invstd, w.coef, C, (float2*)nullptr, shm, shb);
     const float dscale = 1.f / (1.f - drop_p);
-    const float* res = hints.residual;
-    if (res && (drop_p > 0.f || !al16(res))) return UAPS_EINVAL;      // the join has no dropout; the residual is a tensor like y
 #define UAPS_APPLY(V, D) hipLaunchKernelGGL((bn_apply_kernel<V, D>), grid, dim3(kThreads), 0, s, y, out, C, HW, save_mean, w.coef, slope, drop_p, dscale, seed, offset, Bg, (const uint32_t*)uaps_get_step_state(), res, hints.out_amax)
     if (vec) { if (drop_p > 0.f) UAPS_APPLY(true, true); else UAPS_APPLY(true, false); }
     else { if (drop_p > 0.f) UAPS_APPLY(false, true); else UAPS_APPLY(false, false); }
@@ -743,7 +743,8 @@ extern "C" int uaps_bn_act_bwd_prepare(const float* dout, const float* y, const 
                                        const float* save_invstd, float slope, int B, int C, int H, int W, int groups, float* coef,
                                        float* dgamma, float* dbeta, float* dconv_bias, float* dy_bound, void* ws, size_t ws_bytes,
                                        uaps_stream_t stream) {
-    if (!dout || !y || B <= 0 || C <= 0 || H <= 0 || W <= 0) return UAPS_EINVAL;
+    int rc = check(dout, y, B, C, H, W);
+    if (rc) return rc;
     if (!gamma || !beta || !save_mean || !save_invstd || !coef || !dgamma || !dbeta || !dy_bound || !ws) return UAPS_EINVAL;
     if (groups < 1 || groups > kMaxGroups || B % groups) return UAPS_EINVAL;
     const long HW = (long)H * W;
@@ -752,7 +753,7 @@ extern "C" int uaps_bn_act_bwd_prepare(const float* dout, const float* y, const 
     hipStream_t s = (hipStream_t)stream;
     const BnWs w = carve(ws, B, C, HW);
     const int nch = nchunks_for(HW), Bg = B / groups;
-    int rc = uaps_zero_bounds(w.maxes, 2 * UAPS_BOUND_FLOATS, stream);
+    rc = uaps_zero_bounds(w.maxes, 2 * UAPS_BOUND_FLOATS, stream);
     if (rc) return rc;
     const dim3 grid(nch, B * C);
     float* gmax = w.maxes; float* xmax = w.maxes + UAPS_BOUND_FLOATS;

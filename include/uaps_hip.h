@@ -628,6 +628,43 @@ int uaps_softmax_klmap_bwd(const float* a, const float* b, const float* grad_map
 int uaps_entropy_map(const float* p, int B, int C, int H, int W, float* ent_map, float* ent_mean, void* workspace,
                      size_t workspace_bytes, uaps_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mean Teacher (MT/MT_train.py) and uncertainty-aware Mean Teacher (UAMT/UA_MT_train.py): csrc/loss_mean_teacher.hip.
+ * Every tensor below 2 GiB (UAPS_ERANGE otherwise); T in [0, UAPS_MC_MAX_T].
+ *
+ * uaps_ema_update: update_ema_variables (MT_train.py:79-83) over n (ema, param) pairs of any sizes, one launch per 128 pairs:
+ *   ema = ema * alpha + one_minus_alpha * param, the product rounded first (mul_ then add_), alpha = min(1 - 1/(step+1), decay)
+ *   and 1 - alpha formed by the caller in double.  Parameters only; BatchNorm buffers are not averaged (as in the reference).
+ *
+ * uaps_teacher_noise: the (1 + T) B teacher inputs of a UAMT step in one launch, out [(1+T)B, Cin, H, W]:
+ *   out[r] = x[r % B] + clamp(0.1f * n, -0.2f, 0.2f)      (UA_MT_train.py:180-181 rows [0,B); :190-194 rows [B,(1+T)B))
+ *   n ~ N(0,1): Box-Muller on Philox4x32-10 keyed by `seed`, counter offset + i / 4 for flat element i.  T = 0: the B rows of
+ *   MT's teacher input (MT_train.py:181).  _apply: n [(1+T)B, Cin, H, W] given by the caller instead.
+ *
+ * uaps_mc_consistency_fwd: per pixel of the student logits s and teacher logits e [B,C,H,W]
+ *   mc != NULL (mask mode, UA_MT_train.py:194-214): p_bar = mean_t softmax(mc[t]) of the raw MC teacher logits mc [T,B,C,H,W]
+ *     (T > 0), or p_bar = mc [B,C,H,W] (T = 0: already-averaged probabilities); u = -sum_c p_bar log(p_bar + 1e-6);
+ *     m = u < threshold -> mask uint8 [B,H,W] (required), uncertainty [B,1,H,W] (optional);
+ *     out3 = (sum m d / (2 sum m + 1e-16), sum m d, sum m) with d = sum_c (softmax(s) - softmax(e))^2;
+ *   mc == NULL (MT mode, MT_train.py:199): out3 = (mean((softmax(s) - softmax(e))^2), sum d, B H W); T must be 0.
+ *   workspace: uaps_mc_consistency_workspace_bytes().
+ * uaps_mc_consistency_bwd: d(grad[0] * out3[0]) / ds; the teacher gets no gradient.  mask and out3 of the mask-mode forward
+ *   (device pointers: no host sync), or both NULL for MT mode.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_MC_MAX_T 16
+int uaps_ema_update(float* const* ema_host, const float* const* param_host, const long* numel_host, int n, float alpha,
+                    float one_minus_alpha, uaps_stream_t stream);
+int uaps_teacher_noise(const float* x, int B, int Cin, int H, int W, int T, uint64_t seed, uint64_t offset, float* out,
+                       uaps_stream_t stream);
+int uaps_teacher_noise_apply(const float* x, const float* noise, int B, int Cin, int H, int W, int T, float* out,
+                             uaps_stream_t stream);
+int uaps_mc_consistency_workspace_bytes(size_t* out_host);
+int uaps_mc_consistency_fwd(const float* student, const float* teacher, const float* mc, int T, int B, int C, int H, int W,
+                            float threshold, uint8_t* mask, float* uncertainty, float* out3, void* workspace, size_t workspace_bytes,
+                            uaps_stream_t stream);
+int uaps_mc_consistency_bwd(const float* student, const float* teacher, const uint8_t* mask, const float* grad, const float* out3,
+                            int B, int C, int H, int W, float* dstudent, uaps_stream_t stream);
+
 /* Residual join of the ResNet blocks (utilities/resnet.py:47-50, 88-91): out = relu(a + b) over n floats; the
  * backward of both addends is dx = dout * (out > 0). */
 int uaps_add_relu(const float* a, const float* b, float* out, long n, uaps_stream_t stream);

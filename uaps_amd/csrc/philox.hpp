@@ -32,6 +32,14 @@ __device__ __forceinline__ float step_f(const uint32_t* st, int word, float by_v
     return (st && by_value != by_value) ? __uint_as_float(st[word]) : by_value;
 }
 __device__ __forceinline__ float u01(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }   // [0,1)
+// Two standard normal draws from two Philox words (Box-Muller): u1 in (0,1] keeps the logarithm finite (|n| <= 5.77)
+__device__ __forceinline__ float2 gauss2(uint32_t a, uint32_t b) {
+    const float u1 = (float)((a >> 8) + 1u) * (1.0f / 16777216.0f), u2 = u01(b);
+    const float rad = sqrtf(-2.f * logf(u1));
+    float s, c;
+    sincospif(2.f * u2, &s, &c);
+    return make_float2(rad * c, rad * s);
+}
 __device__ __forceinline__ uint32_t pick(const U4& r, int i) { return i == 0 ? r.x : i == 1 ? r.y : i == 2 ? r.z : r.w; }
 }  // namespace uaps
 extern "C" const void* uaps_get_step_state(void);

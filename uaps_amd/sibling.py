@@ -9,6 +9,10 @@
 Per-pixel maps and their gradients are hand-written kernels; the scalar glue between them (means, exp(-v), the mask
 threshold) is the handful of torch element-wise / reduction ops the reference's training scripts spell out.  GPU
 tensors only: like every op of this package these raise `UapsHipError` on CPU tensors or without the HIP library.
+
+The UAMT functions here are the reference-shaped call forms (fixture g8 pins them); the trainers (`mean_teacher.UAMTTrainer`,
+`MeanTeacherTrainer`) use the fused form instead: `mean_teacher.mc_consistency`, one kernel for the Monte-Carlo mean, the
+entropy mask and the masked sums, and one grouped teacher forward for the T noisy passes.
 """
 from __future__ import annotations
 

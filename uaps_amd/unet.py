@@ -214,6 +214,15 @@ class UNet(nn.Module):
             bounds.refresh(self._bns)
         return self.decoder(self.encoder(x))
 
+    def forward_pair(self, x_a, x_b):
+        """The student's two forwards of a Mean Teacher step (MT_train.py:175 labelled, :178 unlabelled) as ONE pass over the
+        concatenated batch, per-half BatchNorm statistics and dropout draws (as UNet_UAPS.forward_pair).  Returns the logits
+        [2B, class_num, H, W]: rows [:B] belong to x_a, rows [B:] to x_b.  GPU only."""
+        if x_a.shape != x_b.shape:
+            raise ValueError("forward_pair: the two batches must have the same shape")
+        with fused.stat_groups(2):
+            return self.forward(fused.cat_batches(x_a, x_b))
+
 
 # perturbation applied in front of auxiliary decoder i (UAPS_unet.py:227-231); decoders beyond the
 # reference's three (the K=5 stress config has no reference implementation) cycle through the same three.

@@ -665,6 +665,42 @@ int uaps_mc_consistency_fwd(const float* student, const float* teacher, const fl
 int uaps_mc_consistency_bwd(const float* student, const float* teacher, const uint8_t* mask, const float* grad, const float* out3,
                             int B, int C, int H, int W, float* dstudent, uaps_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * CCT (CCT/CCT_train.py) and DCT (DCT/DCT_train.py): csrc/loss_cct_dct.hip.  Every tensor below 2 GiB (UAPS_ERANGE otherwise),
+ * C in [2, UAPS_MAX_CLASSES] (UAPS_ERANGE), logits fp32 [*, C, H, W] contiguous.  A window [b0, b0 + B) names rows of a larger batch:
+ * the kernels read (and the backwards write) those rows only.
+ *
+ * uaps_cct_consistency_fwd: D in [2, UAPS_CCT_MAX_HEADS] head logits (host array of device pointers; head 0 the main decoder):
+ *   out[0] = (1/(D-1)) sum_{k>=1} mean((softmax(z0) - softmax(zk))^2), the mean over the window's B C H W elements
+ *   (CCT_train.py:195-200); out[k] = the k-th term's sum (k = 1..D-1).  out: D floats.  Probabilities are never written.
+ *   workspace: uaps_cct_dct_workspace_bytes().
+ * uaps_cct_consistency_bwd: d(grad[0] * out[0]) / dz for every head (nothing is detached in the reference): with
+ *   a = 2 grad[0] / ((D-1) B C H W), g0 = a sum_k (p0 - pk), gk = -a (p0 - pk), dz = p (g - <p, g>), into rows [b0, b0 + B) of the
+ *   caller's D gradient buffers (host array of device pointers).  grad is read on the device (no host sync).
+ *
+ * uaps_rot90_batch: the DCT step's input in one launch (DCT_train.py:165-175): out = [x_l ; x_u ; rot90(x_u, k, [2, 3])] along the
+ *   batch axis, x_l and x_u [B, Cin, H, W], k in [0, 3] (UAPS_EINVAL otherwise).  rot_out == NULL: the rotated batch is rows
+ *   [2B, 3B) of out (needs k even or H == W); else out holds [x_l ; x_u] and rot_out [B, Cin, Ho, Wo] (Ho, Wo = W, H for odd k).
+ *   With uaps_call_hints::out_amax the bound is raised to max|.| of everything written.
+ *
+ * uaps_rot_consistency_fwd: mean((softmax(r) - rot90(softmax(u), k, [2, 3]))^2) over B C H W (DCT_train.py:188): u = rows
+ *   [u_b0, u_b0 + B) of the plain forward's logits [*, C, H, W], r = rows [r_b0, r_b0 + B) of the rotated forward's [*, C, Ho, Wo].
+ *   The rotation is an index map inside the kernel.  out2 = (loss, sum).  workspace: uaps_cct_dct_workspace_bytes().
+ * uaps_rot_consistency_bwd: d(grad[0] * loss) / dr and / du (both sides trained), written into the same windows of dr and du.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_CCT_MAX_HEADS 8
+int uaps_cct_dct_workspace_bytes(size_t* out_host);
+int uaps_cct_consistency_fwd(const float* const* heads_host, int D, int b0, int B, int C, int H, int W, float* out, void* workspace,
+                             size_t workspace_bytes, uaps_stream_t stream);
+int uaps_cct_consistency_bwd(const float* const* heads_host, int D, int b0, int B, int C, int H, int W, const float* grad,
+                             float* const* dheads_host, uaps_stream_t stream);
+int uaps_rot90_batch(const float* x_l, const float* x_u, int B, int Cin, int H, int W, int k, float* out, float* rot_out,
+                     uaps_stream_t stream);
+int uaps_rot_consistency_fwd(const float* r, int r_b0, const float* u, int u_b0, int B, int C, int H, int W, int k, float* out2,
+                             void* workspace, size_t workspace_bytes, uaps_stream_t stream);
+int uaps_rot_consistency_bwd(const float* r, int r_b0, const float* u, int u_b0, int B, int C, int H, int W, int k, const float* grad,
+                             float* dr, float* du, uaps_stream_t stream);
+
 /* Residual join of the ResNet blocks (utilities/resnet.py:47-50, 88-91): out = relu(a + b) over n floats; the
  * backward of both addends is dx = dout * (out > 0). */
 int uaps_add_relu(const float* a, const float* b, float* out, long n, uaps_stream_t stream);
@@ -773,6 +809,8 @@ int uaps_up_cat_fwd_h(const uaps_call_hints* hints, const float* skip, const flo
                       uaps_stream_t stream);
 int uaps_cat2_h(const uaps_call_hints* hints, const float* a, const float* b, float* out, long n, uaps_stream_t stream);
 int uaps_add_relu_h(const uaps_call_hints* hints, const float* a, const float* b, float* out, long n, uaps_stream_t stream);
+int uaps_rot90_batch_h(const uaps_call_hints* hints, const float* x_l, const float* x_u, int B, int Cin, int H, int W, int k, float* out,
+                       float* rot_out, uaps_stream_t stream);
 int uaps_pairloss_bwd_h(const uaps_call_hints* hints, const float* const* lab_logits_host, const float* const* un_logits_host,
                         const int64_t* labels, const int64_t* pseudo, const float* sup_scalars, const float* unsup_scalars, float cw1,
                         float cw2, const float* grad_scale, int D, int B, int C, int H, int W, long n_pixels_loss,

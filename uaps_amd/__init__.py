@@ -12,6 +12,7 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
                                                     UCC_train.py:213-238, UA_MT_train.py:188-214)
   UAPSTrainer                                       (UAPS_train.py:109-450 step/optimizer/checkpoint)
   MeanTeacherTrainer, UAMTTrainer, ema_update, mc_consistency   (MT/MT_train.py, UAMT/UA_MT_train.py)
+  CCTTrainer, DCTTrainer, cct_consistency, rot_consistency, rot90_batch   (CCT/CCT_train.py, DCT/DCT_train.py)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -24,6 +25,7 @@ from .net_factory import net_factory
 from .consistency import (softmax_mse_loss, softmax_kl_loss, kl_loss, entropy_map, entropy_minmization, uncertainty_map)
 from .trainer import UAPSTrainer, BaselineTrainer
 from .mean_teacher import MeanTeacherTrainer, UAMTTrainer, ema_update, mc_consistency
-from . import augment, conv, data, dist, graph, inference, mean_teacher, optim, sibling
+from .cct_dct import CCTTrainer, DCTTrainer, cct_consistency, rot_consistency, rot90_batch
+from . import augment, cct_dct, conv, data, dist, graph, inference, mean_teacher, optim, sibling
 
 __all__ = [n for n in dir() if not n.startswith("_")]

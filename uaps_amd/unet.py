@@ -223,6 +223,25 @@ class UNet(nn.Module):
         with fused.stat_groups(2):
             return self.forward(fused.cat_batches(x_a, x_b))
 
+    def forward_groups(self, batches, groups: Optional[int] = None):
+        """G forwards of equal-shape batches as ONE pass (forward_pair for any G): every group keeps the train-mode BatchNorm
+        statistics and dropout draws of its own forward, and the running statistics are updated group after group, in order.
+        `batches`: a sequence of G batches, or one tensor that already holds them one after the other (`groups` = G; e.g. the
+        output of cct_dct.rot90_batch).  Returns the logits [G B, class_num, H, W].  GPU only."""
+        if torch.is_tensor(batches):
+            G = int(groups or 0)
+            if G < 1 or batches.shape[0] % G:
+                raise ValueError(f"forward_groups: a joined batch of {batches.shape[0]} images is not {groups} equal groups")
+            x = batches
+        else:
+            bs = list(batches)
+            G = len(bs)
+            if G < 1 or any(b.shape != bs[0].shape for b in bs) or (groups is not None and int(groups) != G):
+                raise ValueError("forward_groups: the batches must have one shape")
+            x = bs[0] if G == 1 else (fused.cat_batches(bs[0], bs[1]) if G == 2 else torch.cat(bs, dim=0))
+        with fused.stat_groups(G):
+            return self.forward(x)
+
 
 # perturbation applied in front of auxiliary decoder i (UAPS_unet.py:227-231); decoders beyond the
 # reference's three (the K=5 stress config has no reference implementation) cycle through the same three.
@@ -232,14 +251,19 @@ _PERTURBATIONS = ("noise", "dropout", "feature_dropout")
 class UNet_UAPS(nn.Module):
     """Shared encoder, main decoder on clean features, `n_aux` auxiliary decoders on perturbed
     features; returns (main, aux1, ..., aux_n) logits, each [B, class_num, H, W] fp32
-    (UAPS_unet.py:208-233).  `n_aux=3` is the reference model."""
+    (UAPS_unet.py:208-233).  `n_aux=3` is the reference model.  `aux_dropout_p`: p of the Dropout perturbation in front of
+    the second auxiliary decoder -- 0.5 in UAPS, 0.3 in CCT's UNet_CCT (CCT/CCT_unet.py), otherwise the same network."""
 
     def __init__(self, in_chns: int, class_num: int, n_aux: int = 3,
-                 feature_chns: Sequence[int] = FEATURE_CHANNELS, dropout: Sequence[float] = ENCODER_DROPOUT):
+                 feature_chns: Sequence[int] = FEATURE_CHANNELS, dropout: Sequence[float] = ENCODER_DROPOUT,
+                 aux_dropout_p: float = 0.5):
         super().__init__()
         if not 0 <= n_aux <= 7:
             raise ValueError("n_aux must be in 0..7")
+        if not 0.0 <= float(aux_dropout_p) < 1.0:
+            raise ValueError("aux_dropout_p must be in [0, 1)")
         self.n_aux = n_aux
+        self.aux_dropout_p = float(aux_dropout_p)
         self.encoder = Encoder(in_chns, feature_chns, dropout)
         self.main_decoder = Decoder(class_num, feature_chns)
         for i in range(1, n_aux + 1):
@@ -263,7 +287,7 @@ class UNet_UAPS(nn.Module):
         if kind == "noise":
             return [self._noise(f, groups=groups) for f in feats]
         if kind == "dropout":
-            return [perturb.Dropout(f) for f in feats]
+            return [perturb.Dropout(f, self.aux_dropout_p) for f in feats]
         return [perturb.FeatureDropout(f, groups=groups) for f in feats]
 
     def forward_main(self, x):
@@ -330,7 +354,8 @@ class UNet_UAPS(nn.Module):
                 for blk in (enc.down1, enc.down2, enc.down3, enc.down4, None):
                     # (the fan-in kernel sums at most 8 gradients: clean + n_aux perturbed + the pooled one)
                     pool = blk is not None and _FUSED_POOL and f.shape[2] % 2 == 0 and f.shape[3] % 8 == 0 and self.n_aux + 2 <= 8
-                    fan = perturb.perturbed_fan_out(f, kinds, _groups, self._noise.uniform_range, with_pool=pool)
+                    fan = perturb.perturbed_fan_out(f, kinds, _groups, self._noise.uniform_range, drop_p=self.aux_dropout_p,
+                                                    with_pool=pool)
                     fans.append(fan)
                     if blk is not None:
                         f = blk.maxpool_conv[1](fan[-1]) if pool else blk(f)

@@ -701,6 +701,44 @@ int uaps_rot_consistency_fwd(const float* r, int r_b0, const float* u, int u_b0,
 int uaps_rot_consistency_bwd(const float* r, int r_b0, const float* u, int u_b0, int B, int C, int H, int W, int k, const float* grad,
                              float* dr, float* du, uaps_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * CPS, cross pseudo supervision (CPS/CPS_train.py:195-250): csrc/loss_cps.hip.  z1, z2: fp32 logits [N, C, H, W] (contiguous) of two
+ * networks on one batch whose rows [0, B_lab) are labelled (labels int64 [B_lab, H, W]) and rows [B_lab, N) unlabelled;
+ * 1 <= B_lab < N (UAPS_EINVAL otherwise), C in [2, UAPS_MAX_CLASSES] (UAPS_ERANGE), every tensor below 2 GiB (UAPS_ERANGE).
+ * With CE = nn.CrossEntropyLoss() (mean), Dice = utilities/pytorch_losses.dice_loss (sums over batch and space, mean over the
+ * classes, eps) and p_m = the arg-max over the classes of network m's logits, the LOWEST index among equal logits
+ * (= torch.argmax(softmax(z_m)) except where the fp32 softmax rounds different logits to one probability), the six terms t are
+ *   t = 0, 1   network 1, 2 against the ground truth on the labelled rows                   :215-220
+ *   t = 2, 3   network 1 against p_2, network 2 against p_1 on the labelled rows            :228-232
+ *   t = 4, 5   the same on the unlabelled rows                                              :238-242
+ *   sup = 0.5 (ce_0 + dice_0) + 0.5 (ce_1 + dice_1)                                         :222-224
+ *   labeled_cps = 0.5 ce_2 + 0.5 dice_2 + 0.5 ce_3 + 0.5 dice_3                             :231-234
+ *   cps = 0.5 ce_4 + 0.5 dice_4 + 0.5 ce_5 + 0.5 dice_5                                     :241-245
+ * uaps_cps_fwd: one pass over both tensors + one finalize launch (block partial sums in the workspace, added in double in a fixed
+ *   order: deterministic).  scalars: UAPS_CPS_S_NSCALARS(C) floats in the layout below.  pseudo1, pseudo2: optional uint8 [N, H, W]
+ *   outputs, the arg-max of z1 / z2 at every pixel (NULL: not stored).  A ground-truth label outside [0, C) enters no term and is
+ *   counted in scalars[UAPS_CPS_S_BAD].  workspace: uaps_cps_workspace_bytes().
+ * uaps_cps_bwd: one launch overwrites every row of dz1 and dz2: rows [0, B_lab) with d(g_sup sup + g_lcps labeled_cps) / dz, rows
+ *   [B_lab, N) with d(g_cps cps) / dz.  g_*: device pointers to one float each, NULL = 1 (read on the device: no host sync).
+ *   scalars: what the forward wrote for the same tensors; the pseudo-labels are formed again from the logits (they carry no gradient).
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_CPS_S_CE 0                                     /* ce[6]                                              */
+#define UAPS_CPS_S_DICE 6                                   /* dice[6]                                            */
+#define UAPS_CPS_S_SUP 12
+#define UAPS_CPS_S_LCPS 13
+#define UAPS_CPS_S_CPS 14
+#define UAPS_CPS_S_BAD 15                                   /* number of labels outside [0,C) (must be 0)         */
+#define UAPS_CPS_S_A1(C) 16                                 /* [6][C]  2 / (C (card + eps))                       */
+#define UAPS_CPS_S_A2(C) (16 + 6 * (C))                     /* [6][C]  2 I / (C (card + eps)^2)                   */
+#define UAPS_CPS_S_I(C) (16 + 12 * (C))                     /* [6][C]  Dice intersections  sum p [target = c]     */
+#define UAPS_CPS_S_CARD(C) (16 + 18 * (C))                  /* [6][C]  Dice cardinalities  sum p + #[target = c]  */
+#define UAPS_CPS_S_NSCALARS(C) (16 + 24 * (C))
+int uaps_cps_workspace_bytes(int N, int B_lab, int C, int H, int W, size_t* out_host);
+int uaps_cps_fwd(const float* z1, const float* z2, const int64_t* labels, int N, int B_lab, int C, int H, int W, float eps,
+                 uint8_t* pseudo1, uint8_t* pseudo2, float* scalars, void* workspace, size_t workspace_bytes, uaps_stream_t stream);
+int uaps_cps_bwd(const float* z1, const float* z2, const int64_t* labels, const float* scalars, const float* g_sup, const float* g_lcps,
+                 const float* g_cps, int N, int B_lab, int C, int H, int W, float* dz1, float* dz2, uaps_stream_t stream);
+
 /* Residual join of the ResNet blocks (utilities/resnet.py:47-50, 88-91): out = relu(a + b) over n floats; the
  * backward of both addends is dx = dout * (out > 0). */
 int uaps_add_relu(const float* a, const float* b, float* out, long n, uaps_stream_t stream);

@@ -18,6 +18,7 @@ below from those imported pieces plus the same torch builtins it instantiates at
 lines 73-75, in the same order and association, generalised over the number of heads.
 
 Usage: python tools/make_golden.py            (writes tests/golden/*.npz)
+       python tools/make_golden.py g9         (one fixture)
 """
 import os
 import sys
@@ -464,8 +465,81 @@ def g8():
     np.savez_compressed(os.path.join(OUT, "g8_sibling.npz"), **out)
 
 
+def g9():
+    """CPS (CPS/CPS_train.py, utilities/m_unet.py).  (a) the ordered state_dict keys and shapes of the reference's UNet_f(3, 4);
+    (b) dp0..dp3 of its 9-tuple in eval mode on formula weights (tests/formula_weights.py) for one 1x3x32x32 input; (c) the loss
+    block of CPS_train.py:215-250 on fixed random logits z1, z2 [4,4,24,20] with the first 2 rows labelled: the twelve terms from the
+    reference's dice_loss and nn.CrossEntropyLoss() composed as the script does, torch.argmax(softmax) pseudo-labels, sup,
+    labeled_cps, cps and the autograd gradients of sup + cw * cps + cw * labeled_cps for cw = 0.07.  The script itself imports
+    tensorboardX / cv2 and cannot be imported."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from formula_weights import formula_state_dict, formula_input
+    import utilities.m_unet as R_m
+    torch.manual_seed(0)
+    net = R_m.UNet_f(3, 4)
+    out = {"keys": np.array(list(net.state_dict().keys())), "shapes": np.array([str(tuple(v.shape)) for v in net.state_dict().values()])}
+    net.load_state_dict(formula_state_dict(net.state_dict()))
+    net.eval()
+    x = formula_input((1, 3, 32, 32))
+    with torch.no_grad():
+        tup = net(x)
+    out["x"] = x.numpy()
+    for i in range(4):
+        out[f"dp{i}"] = tup[5 + i].numpy()
+    # ---- (c)
+    N, B_lab, C, H, W, cw = 4, 2, 4, 24, 20, 0.07
+    seed = 31
+    while True:
+        rng = np.random.default_rng(seed)
+        z = [torch.tensor((rng.standard_normal((N, C, H, W)) * 2).astype(np.float32), requires_grad=True) for _ in range(2)]
+        soft = [torch.softmax(t.detach(), dim=1) for t in z]
+        top2 = [torch.topk(s_, 2, dim=1).values for s_ in soft]
+        near = sum(int(((t2[:, 0] - t2[:, 1]) <= 1e-5).sum()) for t2 in top2)
+        if near <= 1e-4 * 2 * N * H * W:        # the condition the GPU parity test relies on (arg-max of logits vs of softmax)
+            break
+        seed += 1
+    labels_S1 = torch.tensor(rect_labels(rng, B_lab, C, H, W))
+    outputs_1, outputs_2 = z[0][:B_lab], z[1][:B_lab]
+    un_outputs_1, un_outputs_2 = z[0][B_lab:], z[1][B_lab:]
+    outputs_1_soft, outputs_2_soft = torch.softmax(outputs_1, dim=1), torch.softmax(outputs_2, dim=1)
+    un_outputs_soft_1, un_outputs_soft_2 = torch.softmax(un_outputs_1, dim=1), torch.softmax(un_outputs_2, dim=1)
+    loss_ce_1 = ce_loss(outputs_1, labels_S1.long())
+    loss_ce_2 = ce_loss(outputs_2, labels_S1.long())
+    loss_dice_1 = R_dice(labels_S1.unsqueeze(1), outputs_1)
+    loss_dice_2 = R_dice(labels_S1.unsqueeze(1), outputs_2)
+    sup_loss = 0.5 * (loss_ce_1 + loss_dice_1) + 0.5 * (loss_ce_2 + loss_dice_2)
+    lbl_pseudo_1 = torch.argmax(outputs_1_soft.detach(), dim=1, keepdim=False)
+    lbl_pseudo_2 = torch.argmax(outputs_2_soft.detach(), dim=1, keepdim=False)
+    t2 = (ce_loss(outputs_1, lbl_pseudo_2), R_dice(lbl_pseudo_2.unsqueeze(1), outputs_1))
+    t3 = (ce_loss(outputs_2, lbl_pseudo_1), R_dice(lbl_pseudo_1.unsqueeze(1), outputs_2))
+    labeled_cps = (0.5 * t2[0] + 0.5 * t2[1]) + (0.5 * t3[0] + 0.5 * t3[1])
+    pseudo_outputs1 = torch.argmax(un_outputs_soft_1.detach(), dim=1, keepdim=False)
+    pseudo_outputs2 = torch.argmax(un_outputs_soft_2.detach(), dim=1, keepdim=False)
+    t4 = (ce_loss(un_outputs_1, pseudo_outputs2), R_dice(pseudo_outputs2.unsqueeze(1), un_outputs_1))
+    t5 = (ce_loss(un_outputs_2, pseudo_outputs1), R_dice(pseudo_outputs1.unsqueeze(1), un_outputs_2))
+    cps_loss = (0.5 * t4[0] + 0.5 * t4[1]) + (0.5 * t5[0] + 0.5 * t5[1])
+    loss = sup_loss + cw * cps_loss + cw * labeled_cps
+    loss.backward()
+    terms = [(loss_ce_1, loss_dice_1), (loss_ce_2, loss_dice_2), t2, t3, t4, t5]
+    out.update(z1=z[0].detach().numpy(), z2=z[1].detach().numpy(), labels=labels_S1.numpy().astype(np.int64), b_lab=np.int64(B_lab),
+               cw=np.float64(cw), seed=np.int64(seed), ce=np.array([float(a) for a, _ in terms], dtype=np.float64),
+               dice=np.array([float(b) for _, b in terms], dtype=np.float64), sup=np.float64(float(sup_loss)),
+               labeled_cps=np.float64(float(labeled_cps)), cps=np.float64(float(cps_loss)), loss=np.float64(float(loss)),
+               dz1=z[0].grad.numpy(), dz2=z[1].grad.numpy(),
+               pseudo1=torch.cat([lbl_pseudo_1, pseudo_outputs1]).numpy().astype(np.uint8),
+               pseudo2=torch.cat([lbl_pseudo_2, pseudo_outputs2]).numpy().astype(np.uint8),
+               gap1=(top2[0][:, 0] - top2[0][:, 1]).numpy(), gap2=(top2[1][:, 0] - top2[1][:, 1]).numpy())
+    np.savez_compressed(os.path.join(OUT, "g9_cps.npz"), **out)
+    print(f"g9 seed {seed} near-ties {near}: sup {float(sup_loss):.6f} labeled_cps {float(labeled_cps):.6f} cps {float(cps_loss):.6f}")
+
+
 def main():
     torch.set_num_threads(4)
+    only = sys.argv[1:]                      # e.g. `python tools/make_golden.py g9`: that fixture alone
+    if only:
+        for name in only:
+            globals()[name]()
+        return
     g1_case("neu", 4, 2, 4, 16, 16, seed=0)
     g1_case("dagm7", 4, 2, 7, 12, 12, seed=1)
     g1_case("kosdd2", 4, 1, 2, 16, 32, seed=2)
@@ -483,6 +557,7 @@ def main():
     g6()
     g7()
     g8()
+    g9()
 
 
 if __name__ == "__main__":

@@ -13,19 +13,21 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   UAPSTrainer                                       (UAPS_train.py:109-450 step/optimizer/checkpoint)
   MeanTeacherTrainer, UAMTTrainer, ema_update, mc_consistency   (MT/MT_train.py, UAMT/UA_MT_train.py)
   CCTTrainer, DCTTrainer, cct_consistency, rot_consistency, rot90_batch   (CCT/CCT_train.py, DCT/DCT_train.py)
+  CPSTrainer, cps_loss, cps_scalars, UNet_f         (CPS/CPS_train.py, utilities/m_unet.py)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
                      sup_scalars)
 from .perturb import FeatureNoise, Dropout, FeatureDropout, manual_seed as perturb_manual_seed
 from .metrics import mIoU, mDice, pixel_accuracy, seg_confusion, seg_confusion_per_image, metrics_from_confusion, mean_batch_metrics
-from .unet import UNet, UNet_UAPS
+from .unet import UNet, UNet_UAPS, UNet_f
 from .res_uaps import ResUAPS, ResNet, resnet50
 from .net_factory import net_factory
 from .consistency import (softmax_mse_loss, softmax_kl_loss, kl_loss, entropy_map, entropy_minmization, uncertainty_map)
 from .trainer import UAPSTrainer, BaselineTrainer
 from .mean_teacher import MeanTeacherTrainer, UAMTTrainer, ema_update, mc_consistency
 from .cct_dct import CCTTrainer, DCTTrainer, cct_consistency, rot_consistency, rot90_batch
-from . import augment, cct_dct, conv, data, dist, graph, inference, mean_teacher, optim, sibling
+from .cps import CPSTrainer, cps_loss, cps_scalars
+from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, sibling
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -137,6 +137,9 @@ SIGNATURES = {
     "uaps_rot90_batch": (C.c_int, [_PTR, _PTR] + [C.c_int] * 5 + [_PTR, _PTR, _PTR]),
     "uaps_rot_consistency_fwd": (C.c_int, [_PTR, C.c_int, _PTR] + [C.c_int] * 6 + [_PTR, _PTR, C.c_size_t, _PTR]),
     "uaps_rot_consistency_bwd": (C.c_int, [_PTR, C.c_int, _PTR] + [C.c_int] * 6 + [_PTR, _PTR, _PTR, _PTR]),
+    "uaps_cps_workspace_bytes": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_size_t)]),
+    "uaps_cps_fwd": (C.c_int, [_PTR] * 3 + [C.c_int] * 5 + [C.c_float] + [_PTR] * 4 + [C.c_size_t, _PTR]),
+    "uaps_cps_bwd": (C.c_int, [_PTR] * 7 + [C.c_int] * 5 + [_PTR] * 3),
 }
 
 

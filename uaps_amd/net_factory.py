@@ -5,12 +5,14 @@ so checkpoints can be inspected anywhere; the loss/perturbation kernels still re
 import torch
 
 from .res_uaps import ResUAPS
-from .unet import UNet, UNet_UAPS
+from .unet import UNet, UNet_UAPS, UNet_f
 
 
 def net_factory(net_type="unet_uaps", in_chns=3, class_num=4, n_aux=3):
     if net_type == "unet":
         net = UNet(in_chns=in_chns, class_num=class_num)
+    elif net_type == "unet_f":                    # utilities/m_unet.py:264 (CPS/CPS_model.py): U-Net with deep-supervision heads
+        net = UNet_f(in_chns=in_chns, class_num=class_num)
     elif net_type == "unet_uaps":
         net = UNet_UAPS(in_chns=in_chns, class_num=class_num, n_aux=n_aux)
     elif net_type == "unet_cct":                  # CCT/net_factory.py: UNet_CCT = UNet_UAPS with the aux Dropout at p = 0.3

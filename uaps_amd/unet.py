@@ -201,18 +201,27 @@ class Decoder(nn.Module):
 class UNet(nn.Module):
     """Single-decoder U-Net (UAPS_unet.py:188-205; same blocks as utilities/baseline_unet.py:159-176)."""
 
+    decoder_cls = Decoder
+
     def __init__(self, in_chns: int, class_num: int, feature_chns: Sequence[int] = FEATURE_CHANNELS):
         super().__init__()
         self.encoder = Encoder(in_chns, feature_chns)
-        self.decoder = Decoder(class_num, feature_chns)
+        self.decoder = self.decoder_cls(class_num, feature_chns)
         self._bns = None
 
-    def forward(self, x):
+    def _refresh_bounds(self, x):
         if x.is_cuda and self.training:          # bounds of the train-mode BatchNorm outputs (conv mode 'h16')
             if self._bns is None:
                 self._bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
             bounds.refresh(self._bns)
+
+    def forward_main(self, x):
+        """The logits of the decoder's classifier `out_conv` (all a plain `UNet` returns)."""
+        self._refresh_bounds(x)
         return self.decoder(self.encoder(x))
+
+    def forward(self, x):
+        return self.forward_main(x)
 
     def forward_pair(self, x_a, x_b):
         """The student's two forwards of a Mean Teacher step (MT_train.py:175 labelled, :178 unlabelled) as ONE pass over the
@@ -221,7 +230,7 @@ class UNet(nn.Module):
         if x_a.shape != x_b.shape:
             raise ValueError("forward_pair: the two batches must have the same shape")
         with fused.stat_groups(2):
-            return self.forward(fused.cat_batches(x_a, x_b))
+            return self.forward_main(fused.cat_batches(x_a, x_b))
 
     def forward_groups(self, batches, groups: Optional[int] = None):
         """G forwards of equal-shape batches as ONE pass (forward_pair for any G): every group keeps the train-mode BatchNorm
@@ -240,7 +249,44 @@ class UNet(nn.Module):
                 raise ValueError("forward_groups: the batches must have one shape")
             x = bs[0] if G == 1 else (fused.cat_batches(bs[0], bs[1]) if G == 2 else torch.cat(bs, dim=0))
         with fused.stat_groups(G):
-            return self.forward(x)
+            return self.forward_main(x)
+
+
+class DecoderDS(Decoder):
+    """`Decoder_mcps` (utilities/m_unet.py:156-210): the Decoder plus 3x3 deep-supervision classifiers on the outputs of up1, up2 and
+    up3 (`out_conv_dp3`, `_dp2`, `_dp1`; `out_conv_dp4` is built by the reference and never called -- kept for the state_dict).
+    Calling the module gives the `out_conv` logits alone, as Decoder does, without touching the deep-supervision heads."""
+
+    def __init__(self, class_num: int, feature_chns: Sequence[int] = FEATURE_CHANNELS):
+        super().__init__(class_num, feature_chns)
+        f = list(feature_chns)
+        for i in (4, 3, 2, 1):                       # registration order of m_unet.py:177-184
+            setattr(self, f"out_conv_dp{i}", nn.Conv2d(f[i], class_num, kernel_size=3, padding=1))
+
+    def forward_all(self, feats: Sequence[torch.Tensor], shape):
+        """m_unet.py:186-210: (x4, f1, f2, f3, f4, dp0, dp1, dp2, dp3) -- the deepest feature, the four UpBlock outputs, the logits
+        and the three deep-supervision logits nearest-interpolated to `shape`."""
+        def head(m, x):
+            y = conv.conv2d(x, m.weight, m.bias) if x.is_cuda else m(x)
+            return F.interpolate(y, shape)
+        f1 = self.up1(feats[4], feats[3])
+        f2 = self.up2(f1, feats[2])
+        f3 = self.up3(f2, feats[1])
+        f4 = self.up4(f3, feats[0])
+        dp0 = conv.conv2d(f4, self.out_conv.weight, self.out_conv.bias) if f4.is_cuda else self.out_conv(f4)
+        return feats[4], f1, f2, f3, f4, dp0, head(self.out_conv_dp1, f3), head(self.out_conv_dp2, f2), head(self.out_conv_dp3, f1)
+
+
+class UNet_f(UNet):
+    """The network CPS trains twice (utilities/m_unet.py:264-282): the `UNet` encoder with `DecoderDS`.  `forward` returns the
+    reference's 9-tuple; `forward_main`, `forward_pair` and `forward_groups` (inherited) return the `dp0` logits only and launch
+    nothing for the deep-supervision heads, which no CPS loss term reads (CPS_train.py:195-207)."""
+
+    decoder_cls = DecoderDS
+
+    def forward(self, x):
+        self._refresh_bounds(x)
+        return self.decoder.forward_all(self.encoder(x), tuple(x.shape[2:]))
 
 
 # perturbation applied in front of auxiliary decoder i (UAPS_unet.py:227-231); decoders beyond the

@@ -12,7 +12,6 @@ import argparse
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -20,40 +19,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 
-def _timed(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
-
-
-def _kernel_ms(fn, reps):
-    from uaps_amd import _lib
-    fn()
-    timers = []
-    for _ in range(reps):
-        with _lib.LaunchTimer() as t:
-            fn()
-        timers.append(t)
-    torch.cuda.synchronize()
-    assert all(t.dispatch for t in timers)
-    return sum(t.elapsed_ms() for t in timers) / reps
-
-
-def _step_ms(tr, data, steps, warmup):
-    for _ in range(warmup):
-        tr.train_step(*data.next())
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        tr.train_step(*data.next())
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3 / steps
+from _timing import _kernel_ms, _step_ms, _timed  # noqa: E402
 
 
 def main():

@@ -10,6 +10,7 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   uncertainty_map                                   (UAPS-Testing.ipynb cell 24)
   sibling.cct_consistency_loss / ucc_pseudo_supervision / uamt_consistency_loss   (CCT_train.py:195-199,
                                                     UCC_train.py:213-238, UA_MT_train.py:188-214)
+  SegTrainer                                        the base of every trainer: optimizer + schedule, step frame, fit, checkpoints
   UAPSTrainer                                       (UAPS_train.py:109-450 step/optimizer/checkpoint)
   MeanTeacherTrainer, UAMTTrainer, ema_update, mc_consistency   (MT/MT_train.py, UAMT/UA_MT_train.py)
   CCTTrainer, DCTTrainer, cct_consistency, rot_consistency, rot90_batch   (CCT/CCT_train.py, DCT/DCT_train.py)
@@ -24,7 +25,7 @@ from .unet import UNet, UNet_UAPS, UNet_f
 from .res_uaps import ResUAPS, ResNet, resnet50
 from .net_factory import net_factory
 from .consistency import (softmax_mse_loss, softmax_kl_loss, kl_loss, entropy_map, entropy_minmization, uncertainty_map)
-from .trainer import UAPSTrainer, BaselineTrainer
+from .trainer import SegTrainer, UAPSTrainer, BaselineTrainer
 from .mean_teacher import MeanTeacherTrainer, UAMTTrainer, ema_update, mc_consistency
 from .cct_dct import CCTTrainer, DCTTrainer, cct_consistency, rot_consistency, rot90_batch
 from .cps import CPSTrainer, cps_loss, cps_scalars

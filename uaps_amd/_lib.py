@@ -366,6 +366,28 @@ def current_stream(device=None) -> int:
     return torch._C._cuda_getCurrentRawStream(idx)
 
 
+class Workspace:
+    """Scratch for a module's kernels: one uint8 buffer per (device index, raw stream), grown on demand (to at least `min_bytes`),
+    never shrunk, never freed.  Every module keeps an instance of its own -- captured graphs hold these pointers, and kernels of
+    different modules are in flight on one stream at once."""
+    __slots__ = ("min_bytes", "bufs", "torch")
+
+    def __init__(self, min_bytes: int = 0):
+        import torch
+        self.min_bytes, self.bufs, self.torch = int(min_bytes), {}, torch
+
+    def get(self, device, nbytes: int):
+        torch = self.torch
+        idx = device.index
+        if idx is None:
+            idx = torch.cuda.current_device()
+        key = (idx, torch._C._cuda_getCurrentRawStream(idx))
+        w = self.bufs.get(key)
+        if w is None or w.numel() < nbytes:
+            w = self.bufs[key] = torch.empty(max(nbytes, self.min_bytes), dtype=torch.uint8, device=device)
+        return w
+
+
 class device_guard:
     """`with device_guard(dev):` = torch.cuda.device(dev), skipped when dev already is the current device (the usual
     case: one process per GPU), which saves a few microseconds on each of the ~700 launches of a step."""

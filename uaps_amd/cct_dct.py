@@ -18,32 +18,19 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, bounds, conv, lazybn, losses, metrics, perturb
-from .ramps import get_current_consistency_weight
-from .trainer import UAPSTrainer, _rng_state_numpy, _rng_state_plain
+from . import _lib, bounds, losses, perturb
+from ._lossutil import _grad_scalar, _logits
+from .trainer import SegTrainer, _rng_state_numpy, _rng_state_plain
 
 MAX_HEADS = 8                  # UAPS_CCT_MAX_HEADS (include/uaps_hip.h)
 
-_ws: Dict[tuple, torch.Tensor] = {}
+_ws = _lib.Workspace()
 
 
 def _workspace(dev: torch.device) -> torch.Tensor:
-    key = (dev.index, _lib.current_stream(dev))
-    w = _ws.get(key)
-    if w is None:
-        n = C.c_size_t()
-        _lib.check(_lib.lib().uaps_cct_dct_workspace_bytes(C.byref(n)), "uaps_cct_dct_workspace_bytes")
-        w = _ws[key] = torch.empty(n.value, dtype=torch.uint8, device=dev)
-    return w
-
-
-def _logits(t: torch.Tensor, what: str) -> torch.Tensor:
-    _lib.require_device(t, what)
-    if t.dtype != torch.float32 or t.dim() != 4:
-        raise ValueError(f"{what}: float32 [N,C,H,W] logits expected, got {t.dtype} {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{what}: contiguous logits expected")
-    return t
+    n = C.c_size_t()
+    _lib.check(_lib.lib().uaps_cct_dct_workspace_bytes(C.byref(n)), "uaps_cct_dct_workspace_bytes")
+    return _ws.get(dev, n.value)
 
 
 # ---- kernel calls ---------------------------------------------------------------------------------------------------------------
@@ -111,10 +98,6 @@ def _sup_bwd(lab, y, scalars, g, dlab):
         rc = _lib.lib().uaps_sup_bwd(_lib.ptr_array(lab), y.data_ptr(), scalars.data_ptr(), 0.5 / D, 0.5 / D, g.data_ptr(), D, B, Cc, H, W,
                                      _lib.ptr_array(dlab), _lib.current_stream(g.device))
     _lib.check(rc, "uaps_sup_bwd")
-
-
-def _grad_scalar(g, ref):
-    return torch.zeros((), dtype=torch.float32, device=ref.device) if g is None else g.contiguous().to(torch.float32)
 
 
 # ---- public wrappers ---------------------------------------------------------------------------------------------------------------
@@ -276,64 +259,40 @@ class _DctStep(torch.autograd.Function):
 
 # ---- trainers ------------------------------------------------------------------------------------------------------------------------
 
-class _ComparisonTrainer(UAPSTrainer):
-    """What CCTTrainer and DCTTrainer share: Adam(lr), ReduceLROnPlateau(max, min_lr 1e-7, patience 40) (CCT_train.py:107-108,
-    DCT_train.py:111-112), cw = consistency * sigmoid_rampup(iter // 150, rampup) with no gate (CCT_train.py:194, DCT_train.py:186),
-    and checkpoints that also hold the perturbation streams (Philox key / counter, numpy's global generator)."""
+class _ComparisonTrainer(SegTrainer):
+    """What CCTTrainer, DCTTrainer and CPSTrainer share beyond SegTrainer (cw = consistency * sigmoid_rampup(iter // 150, rampup)
+    with no gate, CCT_train.py:194, DCT_train.py:186): checkpoints that also hold the perturbation streams -- the Philox (key,
+    counter) of the dropout / noise draws and numpy's global generator (FeatureDropout thresholds)."""
 
-    ramp_divisor_default = 150
-
-    def __init__(self, model: torch.nn.Module, base_lr: float = 1e-3, consistency: float = 0.1, consistency_rampup: float = 200,
-                 seed: int = 1337, ramp_divisor: Optional[int] = None, overlap_comm: bool = True, track_metrics: bool = True):
-        super().__init__(model, base_lr=base_lr, consistency1=consistency, consistency2=0.0, consistency_rampup=consistency_rampup,
-                         ramp_divisor=self.ramp_divisor_default if ramp_divisor is None else int(ramp_divisor), seed=seed,
-                         overlap_comm=overlap_comm, track_metrics=track_metrics, pair_forward=False)
-        self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="max", min_lr=1e-7, patience=40)
-
-    def consistency_weight(self) -> float:
-        return get_current_consistency_weight(self.c1, self.iter_num, self.rampup, self.ramp_divisor)
-
-    def consistency_weights(self):            # (fit() logs cw1 / cw2)
-        return self.consistency_weight(), 0.0
-
-    def _begin(self, x_l, y_l, x_u):
-        if x_l.shape != x_u.shape:
-            raise ValueError(f"{type(self).__name__}: labelled and unlabelled batches of one shape expected "
-                             f"({tuple(x_l.shape)} vs {tuple(x_u.shape)})")
-        if y_l.shape != (x_l.shape[0],) + tuple(x_l.shape[2:]):
-            raise ValueError(f"{type(self).__name__}: labels [B,H,W] expected, got {tuple(y_l.shape)}")
-        if not self.model.training:
-            self.model.train()
-
-    def _finish(self, lab, y_l, s, scalars, cons, cw, D):
-        """After the backward: the optimizer step, the metrics, the step's device scalars."""
-        if self.buckets is not None:
-            self.buckets.finish()
-        self.optimizer.step()
-        if self.track_metrics:
-            self._cms.append(metrics.seg_confusion(lab, y_l))
-        self.iter_num += 1
-        sc = losses.sup_scalars(scalars, D, lab.shape[1])
-        ce, dice = (sc["ce"][0], sc["dice"][0]) if D == 1 else (sc["ce"].sum(), sc["dice"].sum())
-        return {"ce": ce, "dice": dice, "consistency": cons.detach(), "sup": s.detach(), "unsup": (cons * cw).detach(), "cw": cw}
-
-    def state_for_checkpoint(self, epoch: int, best_dice: float, dataparallel_prefix: bool = True) -> Dict:
-        """The reference's keys (epoch, best_dice_1, state_dict, optimizer) plus this package's resume keys and the perturbation
-        streams: the Philox (key, counter) of the dropout / noise draws and numpy's global generator (FeatureDropout thresholds)."""
-        ck = super().state_for_checkpoint(epoch, best_dice, dataparallel_prefix)
+    def _stream_state(self) -> Dict:
         r = perturb.rng()
-        ck["perturb_rng"] = (int(r.seed), int(r.offset))
-        ck["np_global_rng"] = _rng_state_plain(np.random.mtrand._rand)
-        return ck
+        return {"perturb_rng": (int(r.seed), int(r.offset)), "np_global_rng": _rng_state_plain(np.random.mtrand._rand)}
 
-    def load_checkpoint(self, path: str, load_optimizer: bool = True) -> Dict:
-        ck = super().load_checkpoint(path, load_optimizer)
+    def _load_stream_state(self, ck: Dict) -> None:
         if "perturb_rng" in ck:
             r = perturb.rng()
             r.seed, r.offset = (int(v) for v in ck["perturb_rng"])
         if "np_global_rng" in ck:
             np.random.set_state(_rng_state_numpy(ck["np_global_rng"]))
+
+    def state_for_checkpoint(self, epoch: int, best_dice: float, dataparallel_prefix: bool = True) -> Dict:
+        """The reference's keys (epoch, best_dice_1, state_dict, optimizer), this package's resume keys, the perturbation streams."""
+        ck = super().state_for_checkpoint(epoch, best_dice, dataparallel_prefix)
+        ck.update(self._stream_state())
         return ck
+
+    def load_checkpoint(self, path: str, load_optimizer: bool = True) -> Dict:
+        ck = super().load_checkpoint(path, load_optimizer)
+        self._load_stream_state(ck)
+        return ck
+
+
+def _step_scalars(scalars, D, Cc, s, cons, cw, loss) -> Dict:
+    """The device scalars a CCT / DCT step returns: ce and dice summed over the D heads, as the reference logs them."""
+    sc = losses.sup_scalars(scalars, D, Cc)
+    ce, dice = (sc["ce"][0], sc["dice"][0]) if D == 1 else (sc["ce"].sum(), sc["dice"].sum())
+    return {"ce": ce, "dice": dice, "consistency": cons.detach(), "sup": s.detach(), "unsup": (cons * cw).detach(), "cw": cw,
+            "loss": loss.detach()}
 
 
 class CCTTrainer(_ComparisonTrainer):
@@ -351,20 +310,17 @@ class CCTTrainer(_ComparisonTrainer):
     the host float cw; nothing in it synchronises with the host."""
 
     def train_step(self, x_l: torch.Tensor, y_l: torch.Tensor, x_u: torch.Tensor, w=None) -> Dict[str, torch.Tensor]:
-        self._begin(x_l, y_l, x_u)
+        self._check_batches(x_l, x_u, y_l)
         cw = self.consistency_weight()
         B = x_l.shape[0]
         y = y_l.to(torch.int64).contiguous()
-        with lazybn.scope(), conv.deferred_reduces(model=self.model) as step:
-            if self.buckets is not None:
-                self.buckets.step = step
+        with self._step() as backward:
             heads = self.model.forward_pair(x_l, x_u)                                   # CCT_train.py:163 + :170 in one pass
             s, scalars, cons, _ = _CctStep.apply(y, B, *heads)                         # :177-200
             loss = s + cons * cw                                                       # :202
-            self.optimizer.zero_grad(set_to_none=True)                                 # :205
-            loss.backward(gradient=self._unit_gradient(loss))                          # :207
-        self.last = self._finish(heads[0][:B], y_l, s, scalars, cons, cw, len(heads))  # :212
-        self.last["loss"] = loss.detach()
+            backward(loss)                                                             # :205-207; Adam (:212) on leaving
+        self._count(heads[0][:B], y_l)
+        self.last = _step_scalars(scalars, len(heads), heads[0].shape[1], s, cons, cw, loss)
         return self.last
 
 
@@ -390,16 +346,14 @@ class DCTTrainer(_ComparisonTrainer):
 
     def train_step(self, x_l: torch.Tensor, y_l: torch.Tensor, x_u: torch.Tensor, w=None,
                    rot_times: Optional[int] = None) -> Dict[str, torch.Tensor]:
-        self._begin(x_l, y_l, x_u)
+        self._check_batches(x_l, x_u, y_l)
         k = self.draw_rot_times() if rot_times is None else int(rot_times)
         if k not in (0, 1, 2, 3):
             raise ValueError(f"DCTTrainer: rot_times = {k} outside 0..3")
         cw = self.consistency_weight()
         B = x_l.shape[0]
         y = y_l.to(torch.int64).contiguous()
-        with lazybn.scope(), conv.deferred_reduces(model=self.model) as step:
-            if self.buckets is not None:
-                self.buckets.step = step
+        with self._step() as backward:
             batch, rot_x = rot90_batch(x_l, x_u, k)                                     # :174
             if rot_x is None:
                 main = self.model.forward_groups(batch, groups=3)                       # :165, :170, :175 in one pass
@@ -409,10 +363,9 @@ class DCTTrainer(_ComparisonTrainer):
                 rot = self.model(rot_x)
             s, scalars, cons, _ = _DctStep.apply(y, B, k, main, rot)                   # :179-188
             loss = s + cons * cw                                                       # :191
-            self.optimizer.zero_grad(set_to_none=True)                                 # :194
-            loss.backward(gradient=self._unit_gradient(loss))                          # :196
-        self.last = self._finish(main[:B], y_l, s, scalars, cons, cw, 1)               # :197
-        self.last["loss"] = loss.detach()
+            backward(loss)                                                             # :194-196; Adam (:197) on leaving
+        self._count(main[:B], y_l)
+        self.last = _step_scalars(scalars, 1, main.shape[1], s, cons, cw, loss)
         self.last["rot_times"] = k
         return self.last
 

@@ -10,23 +10,18 @@ As in the reference, gradients flow to the first argument only.  GPU tensors onl
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Tuple
 
 import torch
 
 from . import _lib
 
-_ws: Dict[Tuple[int, int], torch.Tensor] = {}
+_ws = _lib.Workspace()
 
 
 def _workspace(dev: torch.device) -> torch.Tensor:
-    key = (dev.index, _lib.current_stream(dev))
-    w = _ws.get(key)
-    if w is None:
-        n = C.c_size_t()
-        _lib.check(_lib.lib().uaps_pair_workspace_bytes(C.byref(n)), "uaps_pair_workspace_bytes")
-        w = _ws[key] = torch.empty(n.value, dtype=torch.uint8, device=dev)
-    return w
+    n = C.c_size_t()
+    _lib.check(_lib.lib().uaps_pair_workspace_bytes(C.byref(n)), "uaps_pair_workspace_bytes")
+    return _ws.get(dev, n.value)
 
 
 def _pair(a: torch.Tensor, b: torch.Tensor, what: str):

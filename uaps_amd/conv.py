@@ -19,7 +19,7 @@ from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import _graddest, lazybn, _lib, bounds, config, stepctx
 
-_ws: Dict[Tuple[int, int], torch.Tensor] = {}
+_ws = _lib.Workspace(min_bytes=1 << 22)
 # packed weights per parameter: id(weight) -> (weakref, version, generation, wf, wb)
 _packed: Dict[int, tuple] = {}
 # Fused / foreach optimizers (and this package's Adam kernel) update parameters without touching Tensor._version, so the version
@@ -150,13 +150,7 @@ def get_mode() -> str:
     return _mode_name
 
 
-def _workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
-    key = (dev.index, _lib.current_stream(dev))
-    w = _ws.get(key)
-    if w is None or w.numel() < nbytes:
-        w = torch.empty(max(nbytes, 1 << 22), dtype=torch.uint8, device=dev)
-        _ws[key] = w
-    return w
+_workspace = _ws.get
 
 
 # ---- deferred weight-gradient reductions ---------------------------------------------------------------------------------------

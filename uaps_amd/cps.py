@@ -12,20 +12,21 @@ except at pixels where the fp32 softmax rounds two different logits to the same 
 from __future__ import annotations
 
 import ctypes as C
-import itertools
 import os
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import _lib, conv, lazybn, losses, metrics
+from . import _lib, conv, losses, metrics
 from . import dist as udist
-from .cct_dct import _ComparisonTrainer, _grad_scalar, _logits
+from ._lossutil import _grad_scalar, _logits
+from .cct_dct import _ComparisonTrainer
+from .trainer import score_validation
 
 MAX_CLASSES = 8                # UAPS_MAX_CLASSES (include/uaps_hip.h)
 TERMS = ("m1_gt", "m2_gt", "m1_lab_pseudo2", "m2_lab_pseudo1", "m1_un_pseudo2", "m2_un_pseudo1")
 
-_ws: Dict[tuple, torch.Tensor] = {}
+_ws = _lib.Workspace()
 
 
 def s_off(Cc: int) -> Dict[str, int]:
@@ -48,11 +49,7 @@ def cps_scalars(scalars: torch.Tensor, Cc: int) -> Dict[str, torch.Tensor]:
 def _workspace(dev: torch.device, N: int, b_lab: int, Cc: int, H: int, W: int) -> torch.Tensor:
     n = C.c_size_t()
     _lib.check(_lib.lib().uaps_cps_workspace_bytes(N, b_lab, Cc, H, W, C.byref(n)), "uaps_cps_workspace_bytes")
-    key = (dev.index, _lib.current_stream(dev))
-    w = _ws.get(key)
-    if w is None or w.numel() < n.value:
-        w = _ws[key] = torch.empty(n.value, dtype=torch.uint8, device=dev)
-    return w
+    return _ws.get(dev, n.value)
 
 
 def _fwd(z1, z2, y, b_lab, want_pseudo=True):
@@ -137,6 +134,11 @@ class CPSTrainer(_ComparisonTrainer):
     (pseudo1, pseudo2: uint8 [2B,H,W], for logging); nothing in it synchronises with the host.
     Single process only: the gradient buckets of `dist` hold one model."""
 
+    plateau_min_lr, plateau_patience = 1e-7, 50          # CPS_train.py:118-119
+    log_keys = ("loss", "ce_1", "dice_1", "ce_2", "dice_2", "cps", "labeled_cps", "sup", "unsup")
+    weight_keys = ("cw",)
+    net_suffixes = ("_1", "_2")
+
     def __init__(self, model1: torch.nn.Module, model2: torch.nn.Module, base_lr: float = 1e-3, consistency: float = 0.1,
                  consistency_rampup: float = 200, seed: int = 1337, ramp_divisor: int = 150, track_metrics: bool = True):
         if udist.world_size() > 1:
@@ -150,9 +152,7 @@ class CPSTrainer(_ComparisonTrainer):
         params2 = list(model2.parameters())
         if params2[0].device != self.device:
             raise ValueError(f"CPSTrainer: both networks on one device expected ({self.device} vs {params2[0].device})")
-        self.optimizer2 = type(self.optimizer)(params2, lr=base_lr)                                        # CPS_train.py:115-116
-        self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="max", min_lr=1e-7, patience=50)     # :118
-        self.scheduler2 = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer2, mode="max", min_lr=1e-7, patience=50)   # :119
+        self.optimizer2, self.scheduler2 = self._new_optimizer(params2, base_lr)                           # CPS_train.py:115-119
         self._cms2: List[torch.Tensor] = []
         self.best_dice = [0.0, 0.0]                       # :457-472 (the reference starts from False == 0)
         self.patience = [0, 0]
@@ -161,30 +161,23 @@ class CPSTrainer(_ComparisonTrainer):
     def models(self) -> Tuple[torch.nn.Module, torch.nn.Module]:
         return self.model, self.model2
 
-    def learning_rates(self) -> Tuple[float, float]:
-        return float(self.optimizer.param_groups[0]["lr"]), float(self.optimizer2.param_groups[0]["lr"])
+    def _networks(self):
+        return (self.model, self.optimizer, self.scheduler), (self.model2, self.optimizer2, self.scheduler2)
 
     def train_step(self, x_l: torch.Tensor, y_l: torch.Tensor, x_u: torch.Tensor, w=None) -> Dict[str, torch.Tensor]:
-        self._begin(x_l, y_l, x_u)
-        if not self.model2.training:
-            self.model2.train()
+        self._check_batches(x_l, x_u, y_l)
         cw = self.consistency_weight()                                                 # :247
         B = x_l.shape[0]
         y = y_l.to(torch.int64).contiguous()
-        with lazybn.scope(), conv.deferred_reduces(conv._allowed_cached(self.model2), model=self.model):
+        with self._step(conv._allowed_cached(self.model2), models=self.models, optimizers=(self.optimizer, self.optimizer2)) as backward:
             z1 = self.model.forward_pair(x_l, x_u)                                      # :195 + :206 in one pass
             z2 = self.model2.forward_pair(x_l, x_u)                                     # :196 + :207
             sup, lcps, cps, scalars, p1, p2 = cps_loss(z1, z2, y, B)                    # :215-245
             loss = sup + cw * cps + cw * lcps                                           # :250
-            self.optimizer.zero_grad(set_to_none=True)                                  # :252-253
-            self.optimizer2.zero_grad(set_to_none=True)
-            loss.backward(gradient=self._unit_gradient(loss))                           # :255
-        self.optimizer.step()                                                           # :260-261
-        self.optimizer2.step()
-        if self.track_metrics:                                                          # :274-278
-            self._cms.append(metrics.seg_confusion(z1[:B], y_l))
+            backward(loss)                                                              # :252-255; both Adams (:260-261) on leaving
+        self._count(z1[:B], y_l)                                                        # :274-278
+        if self.track_metrics:
             self._cms2.append(metrics.seg_confusion(z2[:B], y_l))
-        self.iter_num += 1
         sc = cps_scalars(scalars, z1.shape[1])
         self.last = {"loss": loss.detach(), "ce_1": sc["ce"][0], "dice_1": sc["dice"][0], "ce_2": sc["ce"][1], "dice_2": sc["dice"][1],
                      "cps": cps.detach(), "labeled_cps": lcps.detach(), "sup": sup.detach(), "unsup": (cw * cps + cw * lcps).detach(),
@@ -193,11 +186,10 @@ class CPSTrainer(_ComparisonTrainer):
 
     def epoch_metrics2(self, reset: bool = True) -> Dict[str, float]:
         """`epoch_metrics` of network 2 (CPS_train.py:277-278, 299-300)."""
-        keep, self._cms = self._cms, self._cms2
-        try:
-            return self.epoch_metrics(reset)
-        finally:
-            self._cms2, self._cms = self._cms, keep
+        return self._score_steps(self._cms2, reset)
+
+    def _train_metrics(self):
+        return self.epoch_metrics(), self.epoch_metrics2()
 
     @torch.no_grad()
     def validate(self, batches, pooled: bool = False) -> Dict[str, float]:
@@ -219,81 +211,23 @@ class CPSTrainer(_ComparisonTrainer):
         ce = torch.stack(ces).double().cpu().numpy()
         self.check_errors()
         out: Dict[str, float] = {"loss": 0.0}
-        for i, s in enumerate(("_1", "_2")):
-            cmi, cei = cm[i::2], ce[i::2]
-            n = len(cmi)
-            if pooled:
-                m = metrics.metrics_from_confusion(cmi.sum(0))
-                dl = 1 - m["mdice"]
-                out.update({k + s: float(m[k]) for k in ("miou", "mdice", "acc")})
-                out["loss"] += 0.5 * (dl + float(cei.mean()))
-            else:
-                per = [metrics.metrics_from_confusion(c) for c in cmi]
-                out.update({k + s: float(sum(p[k] for p in per) / n) for k in ("miou", "mdice", "acc")})           # :407-413
-                dl = float(sum(1 - p["mdice"] for p in per) / n)                                                    # :369, 401
-                out["loss"] += float(sum(0.5 * ((1 - p["mdice"]) + c) for p, c in zip(per, cei)) / n)               # :377, 400
-            out["ce" + s], out["dice_loss" + s] = float(cei.mean()), dl
+        for i, s in enumerate(self.net_suffixes):
+            m = score_validation(cm[i::2], ce[i::2], pooled)
+            out["loss"] += float(m.pop("loss"))
+            out.update({k + s: float(v) for k, v in m.items()})
         return out
 
-    def note_validation(self, mdice_1: float, mdice_2: float) -> Tuple[bool, bool]:
-        """CPS_train.py:414-415, 457-472: each network's scheduler is stepped on its own validation mDice, and each network is saved
-        when its mDice is STRICTLY above its best so far.  Returns (save network 1, save network 2)."""
-        self.scheduler.step(mdice_1)
-        self.scheduler2.step(mdice_2)
-        save = []
-        for i, v in enumerate((mdice_1, mdice_2)):
-            if self.best_dice[i] < v:
-                self.best_dice[i], self.patience[i] = v, 0
-                save.append(True)
-            else:
-                self.patience[i] += 1
-                save.append(False)
-        return save[0], save[1]
-
-    def fit(self, train_batches, unlabeled_batches, val_batches, epochs: int = 800, iter_per_epoch: int = 60,
-            checkpoint_path: Optional[str] = None, start_epoch: int = 1, best_dice=None, log: Optional[Callable[[Dict], None]] = None):
-        """The reference's `run()` (CPS_train.py:133-512) around `train_step`, with the conventions of UAPSTrainer.fit: epochs - 1
-        epochs of iter_per_epoch - 1 steps drawn from zip(cycle(train), cycle(unlabeled)) (:174 cycles the labelled loader only and
-        stops with the unlabelled one), logged means divided by iter_per_epoch (:297-308), nothing inside an epoch synchronising with
-        the host.  `checkpoint_path`: a (path 1, path 2) pair, or one path "x.pth" that becomes "x_1.pth" / "x_2.pth" (the reference
-        writes CPS_10p_1.pth / CPS_10p_2.pth, :487, :498).  `best_dice`: the pair to resume from (the checkpoints' best_dice_1 /
-        best_dice_2)."""
+    # -- fit(): SegTrainer's loop, per network one scheduler, one strict-'>' rule (note_validation) and one file --
+    def _fit_begin(self, best_dice, checkpoint_path):
+        """`checkpoint_path`: a (path 1, path 2) pair, or one path "x.pth" that becomes "x_1.pth" / "x_2.pth" (the reference writes
+        CPS_10p_1.pth / CPS_10p_2.pth, CPS_train.py:487, :498).  `best_dice`: the pair to resume from (the checkpoints' best_dice_1 /
+        best_dice_2); None keeps the trainer's bookkeeping."""
         if best_dice is not None:
             self.best_dice = [float(best_dice[0]), float(best_dice[1])]
-        paths = checkpoint_paths(checkpoint_path)
-        keys = ("loss", "ce_1", "dice_1", "ce_2", "dice_2", "cps", "labeled_cps", "sup", "unsup")
-        history = []
-        for epoch in range(int(start_epoch), int(epochs)):
-            semi = iter(zip(itertools.cycle(train_batches), itertools.cycle(unlabeled_batches)))
-            kept = []
-            for _ in range(1, int(iter_per_epoch)):
-                (x_l, y_l), u = next(semi)
-                x_u = u[0] if isinstance(u, (tuple, list)) else u
-                res = self.train_step(x_l.to(self.device), y_l.to(self.device), x_u.to(self.device))
-                kept.append(torch.stack([res[k].float() for k in keys]))
-            lr1, lr2 = self.learning_rates()
-            rec: Dict = {"epoch": epoch, "iter_num": self.iter_num, "lr_1": lr1, "lr_2": lr2}
-            if kept:
-                sums = torch.stack(kept).sum(0).double().cpu().numpy()
-                rec.update({k: float(v) / iter_per_epoch for k, v in zip(keys, sums)})
-                n = len(kept)
-                for s, tm in (("_1", self.epoch_metrics()), ("_2", self.epoch_metrics2())):
-                    rec["train_miou" + s], rec["train_mdice" + s] = tm["miou"] * n / iter_per_epoch, tm["mdice"] * n / iter_per_epoch
-            rec["cw"] = self.consistency_weight()
-            val = self.validate(val_batches)
-            rec.update({"val_" + k: v for k, v in val.items()})
-            save = self.note_validation(val["mdice_1"], val["mdice_2"])                                     # :414-415, :457-472
-            rec["saved_1"], rec["saved_2"] = save
-            if paths is not None:
-                for i in (0, 1):
-                    if save[i]:
-                        self.save_checkpoint(paths[i], epoch, which=i + 1)                                  # :479-498
-            rec["best_dice_1"], rec["best_dice_2"] = self.best_dice
-            rec["patience_1"], rec["patience_2"] = self.patience
-            history.append(rec)
-            if log is not None:
-                log(rec)
-        return history
+        return checkpoint_paths(checkpoint_path)
+
+    def _save_network(self, i: int, path: str, epoch: int) -> None:
+        self.save_checkpoint(path, epoch, which=i + 1)                                                      # :479-498
 
     # -- checkpoints (CPS_train.py:479-498): one file per network --
     def state_for_checkpoint(self, epoch: int, best_dice: Optional[float] = None, dataparallel_prefix: bool = False, which: int = 1) -> Dict:
@@ -303,15 +237,9 @@ class CPSTrainer(_ComparisonTrainer):
         if which not in (1, 2):
             raise ValueError(f"CPSTrainer: network {which}, expected 1 or 2")
         i = which - 1
-        opt, sch, model = (self.optimizer, self.scheduler, self.model) if i == 0 else (self.optimizer2, self.scheduler2, self.model2)
-        swap = (self.optimizer, self.scheduler, self.model)
-        self.optimizer, self.scheduler, self.model = opt, sch, model
-        try:
-            ck = super().state_for_checkpoint(epoch, self.best_dice[i] if best_dice is None else best_dice, dataparallel_prefix)
-        finally:
-            self.optimizer, self.scheduler, self.model = swap
-        if which == 2:
-            ck["best_dice_2"] = ck.pop("best_dice_1")
+        ck = self._net_state(self._networks()[i], epoch, "best_dice" + self.net_suffixes[i],
+                             self.best_dice[i] if best_dice is None else best_dice, dataparallel_prefix)
+        ck.update(self._stream_state())
         ck["patience"] = int(self.patience[i])
         return ck
 
@@ -328,16 +256,13 @@ class CPSTrainer(_ComparisonTrainer):
         torch.save(self.state_for_checkpoint(epoch, best_dice, which=which), path)
 
     def load_checkpoint(self, path, load_optimizer: bool = True) -> Tuple[Dict, Dict]:
-        """Resume both networks from the two files (`path` as in `fit`).  The perturbation streams are taken from network 1's file
-        (both files of one save hold the same)."""
+        """Resume both networks from the two files (`path` as in `fit`).  The iteration counter and the perturbation streams are
+        taken from network 1's file (both files of one save hold the same)."""
         paths = checkpoint_paths(path)
-        swap = (self.optimizer, self.scheduler, self.model)
-        self.optimizer, self.scheduler, self.model = self.optimizer2, self.scheduler2, self.model2
-        try:
-            ck2 = super().load_checkpoint(paths[1], load_optimizer)
-        finally:
-            self.optimizer, self.scheduler, self.model = swap
-        ck1 = super().load_checkpoint(paths[0], load_optimizer)
+        net1, net2 = self._networks()
+        ck2 = self._load_net_state(net2, paths[1], load_optimizer)
+        ck1 = self._load_net_state(net1, paths[0], load_optimizer)
+        self._load_stream_state(ck1)
         for i, (ck, key) in enumerate(((ck1, "best_dice_1"), (ck2, "best_dice_2"))):
             if key in ck:
                 self.best_dice[i] = float(ck[key])

@@ -4,7 +4,7 @@ fused BatchNorm(train) + LeakyReLU + Dropout and bilinear-x2 + channel concat, w
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Tuple
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -12,7 +12,7 @@ import torch.nn as nn
 from . import _graddest, lazybn, _lib, bounds, stepctx
 from . import perturb as _perturb
 
-_ws: Dict[Tuple[int, int], torch.Tensor] = {}
+_ws = _lib.Workspace(min_bytes=1 << 20)
 
 # Number of statistics groups of the train-mode BatchNorms: the batch is `_groups()` consecutive blocks, each
 # normalised on its own (UNet_UAPS.forward_pair runs the labelled and the unlabelled batch of a step as one
@@ -37,19 +37,10 @@ class stat_groups:
         return False
 
 
-def _workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
-    key = (dev.index, _lib.current_stream(dev))
-    w = _ws.get(key)
-    if w is None or w.numel() < nbytes:
-        w = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
-        _ws[key] = w
-    return w
-
-
 def _bn_ws(dev, B, Cc, H, W):
     n = C.c_size_t()
     _lib.check(_lib.lib().uaps_bn_workspace_bytes(B, Cc, H, W, C.byref(n)), "uaps_bn_workspace_bytes")
-    return _workspace(dev, n.value)
+    return _ws.get(dev, n.value)
 
 
 class _BnActTrain(torch.autograd.Function):

@@ -10,7 +10,7 @@ from __future__ import annotations
 import os
 
 import ctypes as C
-from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -34,7 +34,7 @@ def _s_off(D, C):
             "card": b + 3 * D * C, "cnt": b + 4 * D * C, "n": b + 4 * D * C + C}
 
 
-_ws_cache: Dict[Tuple[int, int], torch.Tensor] = {}
+_workspace = _lib.Workspace().get      # (device, nbytes): scratch for the block partial sums
 
 # bench.py sets this to a dict {kernel name: [(start_event, end_event), ...]} to time individual launches with HIP events
 # attached to the main kernel's dispatch (_lib.LaunchTimer: the pair-loss entries time pair_fwd_kernel / pair_bwd_kernel, the
@@ -60,16 +60,6 @@ class _timed:
             if KERNEL_EVENTS is not None:
                 KERNEL_EVENTS.setdefault(self.name, []).append((self.t.start, self.t.stop))
         return False
-
-
-def _workspace(device: torch.device, nbytes: int) -> torch.Tensor:
-    """Per (device, stream) scratch for the block partial sums; grown on demand, never shrunk."""
-    key = (device.index if device.index is not None else torch.cuda.current_device(), _lib.current_stream(device))
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _ws_cache[key] = ws
-    return ws
 
 
 def _check_heads(logits: Sequence[torch.Tensor], what: str):

@@ -16,9 +16,9 @@ from typing import Dict, Optional, Tuple
 
 import torch
 
-from . import _lib, conv, fused, lazybn, losses, metrics, perturb, sibling
-from .ramps import get_current_consistency_weight
-from .trainer import UAPSTrainer, load_state_dict_any_prefix
+from . import _lib, conv, fused, losses, perturb, sibling
+from ._lossutil import _Halves
+from .trainer import SegTrainer, _module_prefixed, load_state_dict_any_prefix
 
 MAX_T = 16                     # UAPS_MC_MAX_T (include/uaps_hip.h)
 # The teacher noise draws from the Philox key perturb.manual_seed(seed, rank) sets, at counters of its own: the perturbation and
@@ -135,17 +135,13 @@ def teacher_inputs(x_u: torch.Tensor, T: int, rng: Optional[perturb.RngState] = 
 
 # ---- fused consistency --------------------------------------------------------------------------------------------------------------
 
-_ws: Dict[tuple, torch.Tensor] = {}
+_ws = _lib.Workspace()
 
 
 def _workspace(dev: torch.device) -> torch.Tensor:
-    key = (dev.index, _lib.current_stream(dev))
-    w = _ws.get(key)
-    if w is None:
-        n = C.c_size_t()
-        _lib.check(_lib.lib().uaps_mc_consistency_workspace_bytes(C.byref(n)), "uaps_mc_consistency_workspace_bytes")
-        w = _ws[key] = torch.empty(n.value, dtype=torch.uint8, device=dev)
-    return w
+    n = C.c_size_t()
+    _lib.check(_lib.lib().uaps_mc_consistency_workspace_bytes(C.byref(n)), "uaps_mc_consistency_workspace_bytes")
+    return _ws.get(dev, n.value)
 
 
 class _McConsistency(torch.autograd.Function):
@@ -246,25 +242,7 @@ uamt_threshold = sibling.uamt_threshold
 
 # ---- trainers ------------------------------------------------------------------------------------------------------------------------
 
-class _Halves(torch.autograd.Function):
-    """rows [:B] and [B:] of forward_pair's logits; their two gradients are joined by one kernel (fused.cat_batches)."""
-
-    @staticmethod
-    def forward(ctx, both, B):
-        ctx.B = B
-        return both[:B], both[B:]
-
-    @staticmethod
-    def backward(ctx, ga, gb):
-        if ga is None and gb is None:
-            return None, None
-        ref = ga if ga is not None else gb
-        ga = ga.contiguous() if ga is not None else torch.zeros_like(ref)
-        gb = gb.contiguous() if gb is not None else torch.zeros_like(ref)
-        return fused.cat_batches(ga, gb), None
-
-
-class MeanTeacherTrainer(UAPSTrainer):
+class MeanTeacherTrainer(SegTrainer):
     """Mean Teacher (MT/MT_train.py:117-226) on the single-decoder U-Net of BaselineTrainer.  One `train_step` (:175-219):
 
       1. the student's labelled and unlabelled forwards as one pass (UNet.forward_pair);
@@ -284,23 +262,14 @@ class MeanTeacherTrainer(UAPSTrainer):
     def __init__(self, model: torch.nn.Module, ema_model: torch.nn.Module, base_lr: float = 1e-3, ema_decay: float = 0.99,
                  consistency: float = 0.1, consistency_rampup: float = 200, seed: int = 1337, ramp_divisor: Optional[int] = None,
                  overlap_comm: bool = True, track_metrics: bool = True):
-        super().__init__(model, base_lr=base_lr, consistency1=consistency, consistency2=0.0, consistency_rampup=consistency_rampup,
-                         ramp_divisor=self.ramp_divisor_default if ramp_divisor is None else int(ramp_divisor), seed=seed,
-                         overlap_comm=overlap_comm, track_metrics=track_metrics, pair_forward=False)
-        self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode="max", min_lr=1e-7, patience=40)
-        self.n_heads = 1
+        super().__init__(model, base_lr=base_lr, consistency=consistency, consistency_rampup=consistency_rampup,
+                         ramp_divisor=ramp_divisor, seed=seed, overlap_comm=overlap_comm, track_metrics=track_metrics)
         self.ema_model = ema_model
         self.ema_decay = float(ema_decay)
         for p in ema_model.parameters():      # the teacher is never trained (MT_model.py: ema_model parameters detached)
             p.requires_grad_(False)
         # the teacher noise: perturb.manual_seed(seed, rank)'s key, counters of its own (ranks draw different noise)
         self.noise_rng = perturb.RngState(perturb._mix(seed, self.rank), NOISE_STREAM)
-
-    def consistency_weight(self) -> float:
-        return get_current_consistency_weight(self.c1, self.iter_num, self.rampup, self.ramp_divisor)
-
-    def consistency_weights(self):            # (fit() logs cw1 / cw2)
-        return self.consistency_weight(), 0.0
 
     def _teacher(self, x_u, teacher_noise):
         """(teacher logits on the noisy batch, Monte-Carlo logits [T*B,C,H,W] or None), no autograd."""
@@ -325,33 +294,21 @@ class MeanTeacherTrainer(UAPSTrainer):
     def train_step(self, x_l: torch.Tensor, y_l: torch.Tensor, x_u: torch.Tensor, w=None,
                    teacher_noise: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """`teacher_noise`: the recorded n of every teacher input row, [(1 + T) B, Cin, H, W] (tests); default: drawn on the device."""
-        if x_l.shape != x_u.shape:
-            raise ValueError(f"{type(self).__name__}: labelled and unlabelled batches of one shape expected "
-                             f"({tuple(x_l.shape)} vs {tuple(x_u.shape)})")
-        if not self.model.training:
-            self.model.train()
+        self._check_batches(x_l, x_u)
         if not self.ema_model.training:
             self.ema_model.train()                   # the reference never switches its teacher to eval mode
         cw = self.consistency_weight()
         gated = self.iter_num < self.gate_iters
         B = x_l.shape[0]
-        with lazybn.scope(), conv.deferred_reduces(model=self.model) as step:
-            if self.buckets is not None:
-                self.buckets.step = step
+        with self._step() as backward:
             lab, un = _Halves.apply(self.model.forward_pair(x_l, x_u), B)    # MT_train.py:175 + :178 in one pass
             e, mc = self._teacher(x_u, teacher_noise)
             s = losses.uaps_sup_loss((lab,), y_l)                              # :189-192, 0.5 * (dice + CE)
             cons, wc, thr = self._consistency(un, e, mc, cw)
             loss = s.loss + cons * wc                                         # :202
-            self.optimizer.zero_grad(set_to_none=True)                        # :205
-            loss.backward(gradient=self._unit_gradient(loss))                 # :207
-        if self.buckets is not None:
-            self.buckets.finish()
-        self.optimizer.step()                                                 # :212
+            backward(loss)                                                    # :205-207; Adam (:212) on leaving
         ema_update(self.ema_model, self.model, self.ema_decay, self.iter_num)  # :219
-        if self.track_metrics:
-            self._cms.append(metrics.seg_confusion(lab, y_l))
-        self.iter_num += 1
+        self._count(lab, y_l)
         sc = losses.sup_scalars(s.scalars, 1, lab.shape[1])
         self.last = {"loss": loss.detach(), "ce": sc["ce"][0], "dice": sc["dice"][0],
                      "consistency": (cons * 0.0 if gated else cons).detach(),     # MT_train.py:197: 0.0 under the gate
@@ -364,10 +321,7 @@ class MeanTeacherTrainer(UAPSTrainer):
         """The reference's keys (epoch, best_dice_1, state_dict, optimizer; UA_MT_train.py:349-354, MT_train.py likewise) plus
         `ema_state_dict` (the teacher, parameters and BatchNorm buffers) and this package's resume keys."""
         ck = super().state_for_checkpoint(epoch, best_dice, dataparallel_prefix)
-        sd = self.ema_model.state_dict()
-        if dataparallel_prefix and not any(k.startswith("module.") for k in sd):
-            sd = {"module." + k: v for k, v in sd.items()}
-        ck["ema_state_dict"] = sd
+        ck["ema_state_dict"] = _module_prefixed(self.ema_model.state_dict(), dataparallel_prefix)
         ck["teacher_noise_rng"] = (int(self.noise_rng.seed), int(self.noise_rng.offset))
         return ck
 

@@ -13,7 +13,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
-from typing import Dict, Optional, Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -264,7 +264,7 @@ def Dropout(x: torch.Tensor, p: float = 0.5, return_keep: bool = False):
 
 # ---- FeatureDropout -------------------------------------------------------------------------------
 
-_fd_ws: Dict[Tuple[int, int], torch.Tensor] = {}
+_fd_ws = _lib.Workspace()
 
 
 class _FeatDrop(torch.autograd.Function):
@@ -283,11 +283,7 @@ class _FeatDrop(torch.autograd.Function):
         L = _lib.lib()
         need = C.c_size_t()
         _lib.check(L.uaps_feat_dropout_workspace_bytes(Bg, Cc, H, W, C.byref(need)), "uaps_feat_dropout_workspace_bytes")
-        key = (x.device.index, _lib.current_stream(x.device))
-        ws = _fd_ws.get(key)
-        if ws is None or ws.numel() < need.value:
-            ws = torch.empty(need.value, dtype=torch.uint8, device=x.device)
-            _fd_ws[key] = ws
+        ws = _fd_ws.get(x.device, need.value)
         y = torch.empty_like(x)
         keep = torch.empty((B, H, W), dtype=torch.uint8, device=x.device)
         with _lib.device_guard(x.device):
@@ -373,10 +369,7 @@ class _PerturbFan(torch.autograd.Function):
                 else:
                     need = C.c_size_t()
                     _lib.check(L.uaps_feat_dropout_workspace_bytes(B, Cc, H, W, C.byref(need)), "uaps_feat_dropout_workspace_bytes")
-                    key = (dev.index, _lib.current_stream(dev))
-                    ws = _fd_ws.get(key)
-                    if ws is None or ws.numel() < need.value:
-                        ws = _fd_ws[key] = torch.empty(need.value, dtype=torch.uint8, device=dev)
+                    ws = _fd_ws.get(dev, need.value)      # (keyed by the main stream although the fan's side stream uses it)
                     kp[i] = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
                     if DEVICE_THRESHOLDS:
                         us = [-1.0] * groups
@@ -432,10 +425,7 @@ class _PerturbFan(torch.autograd.Function):
                 elif kind == "feature_dropout":
                     need = C.c_size_t()
                     _lib.check(L.uaps_feat_dropout_workspace_bytes(Bg, Cc, H, W, C.byref(need)), "uaps_feat_dropout_workspace_bytes")
-                    key = (dev.index, st)
-                    ws = _fd_ws.get(key)
-                    if ws is None or ws.numel() < need.value:
-                        ws = _fd_ws[key] = torch.empty(need.value, dtype=torch.uint8, device=dev)
+                    ws = _fd_ws.get(dev, need.value)
                     keep = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
                     for g in range(groups):
                         o = g * Bg * chw * 4

@@ -169,8 +169,12 @@ int uaps_subsample2_bwd(const float* dy, float* dx, long planes, int H, int W, u
 /* ---------------------------------------------------------------------------------------------
  * The whole loss block of one training step -- UAPS_train.py:194-218 on the labelled logits and :186-189, 223-282 on the
  * unlabelled logits -- as ONE forward launch (+ a one-block finalize) and ONE backward launch: the first blocks of the
- * grid run the supervised branch, the rest the unsupervised branch; results are bit-identical to uaps_sup_* +
- * uaps_unsup_* (same per-branch block partitioning and fixed-order reductions).  lab_logits / un_logits: D host pointers
+ * grid run the supervised branch, the rest the unsupervised branch.  Against uaps_sup_* + uaps_unsup_*: the pseudo-labels
+ * are bit-identical, the variance maps agree to a few ulp (the instantiations contract their multiply-adds differently), and the
+ * reduced scalars and the gradients that depend on them agree to fp32 summation-order accuracy -- the persistent blocks
+ * partition the pixels differently (tests/test_gpu_pairloss.py, tests/test_gpu_loss_forms.py).  Every launch is bitwise
+ * reproducible run to run, and the backward writes the same gradient bits with and without uaps_call_hints::out_amax.
+ * lab_logits / un_logits: D host pointers
  * each, [B,C,H,W] fp32; ce_coef = dice_coef = 0.5 / D (UAPS_train.py:208-218).  `cfg` = 0, or a cap on the blocks per branch.
  *
  * Gathered-batch semantics.  The reference's nn.DataParallel (UAPS_model.py:13) gathers the logits of all GPUs and computes

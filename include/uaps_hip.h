@@ -743,6 +743,60 @@ int uaps_cps_fwd(const float* z1, const float* z2, const int64_t* labels, int N,
 int uaps_cps_bwd(const float* z1, const float* z2, const int64_t* labels, const float* scalars, const float* g_sup, const float* g_lcps,
                  const float* g_cps, int N, int B_lab, int C, int H, int W, float* dz1, float* dz2, uaps_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * UCC, uncertainty-guided cross-head co-training with cross-cut-mix (UCC/UCC_train.py:147-256, UCC/cross_cutmix.py): csrc/loss_ucc.hip.
+ * C in [2, UAPS_MAX_CLASSES] (UAPS_ERANGE), every tensor below 2 GiB (UAPS_ERANGE).
+ *
+ * uaps_ucc_cutmix_batch: the step's input in one launch.  x_l, x_wk, x_st: fp32 [B, Cin, H, W] (labelled, weakly and strongly augmented
+ *   unlabelled batch), y_l int64 [B, H, W]; rects_l, rects_u: HOST arrays of B x 5 int32 (flag, y0, y1, x0, x1), the rectangle
+ *   [y0, y1) x [x0, x1) of generate_mix_data / generate_crossmix_data's cut-out mask and whether the image is mixed; 0 <= y0 <= y1 <= H
+ *   and 0 <= x0 <= x1 <= W (UAPS_EINVAL otherwise), B <= UAPS_UCC_MAX_BATCH (UAPS_ERANGE): the rectangles travel as kernel arguments,
+ *   nothing is copied to the device and nothing waits for it.  With in_1 / in_2 = pixel inside image i's rectangle of list 1 / 2 with
+ *   its flag set:   out[i] = in_1 ? x_l[(i+1) % B] : x_l[i] (y_out[i] likewise)          cross_cutmix.py:90-91
+ *                   out[B+i] = in_2 ? out[i] : x_wk[i],  out[2B+i] = in_2 ? out[i] : x_st[i]        :115-116 (UCC_train.py:153)
+ *   out: [3B, Cin, H, W], y_out: int64 [B, H, W].  Values are selected, so the result equals the reference's a mask + b (1 - mask) as
+ *   numbers (a -0.0 stays -0.0 here).  With uaps_call_hints::out_amax the bound is raised to max|out|.
+ *
+ * z1, z2: fp32 logits [3B, C, H, W] (contiguous) of the two heads, rows [0, B) the mixed labelled batch (labels int64 [B, H, W]),
+ * [B, 2B) the weak and [2B, 3B) the strong unlabelled batch.  CE / Dice as for CPS; pseudo_1 = arg-max of z2_wk, pseudo_2 = arg-max of
+ * z1_wk over the LOGITS, the lowest index among equals (:224-225).  v1 = sum_c KL(log_softmax z1_wk || softmax z2_st) (:213),
+ * v2 likewise from (z1_st, z2_wk) (:216), M = B H W.  Terms t: 0, 1 = head 1, 2 against the labels; 2 = z1_st against pseudo_1;
+ * 3 = z2_st against pseudo_2.
+ *   sup = 0.5 (ce_0 + dice_0) + 0.5 (ce_1 + dice_1)                                        :197-202
+ *   ps_1 = 0.5 (ce_2 + dice_2) mean exp(-v1) + mean v1,  ps_2 = 0.5 (ce_3 + dice_3) mean exp(-v2) + mean v2,  ps = ps_1 + ps_2   :233-240
+ * uaps_ucc_fwd: one pass over both tensors + one finalize launch (block partial sums in the workspace, added in double in a fixed
+ *   order: deterministic).  scalars: UAPS_UCC_S_NSCALARS(C) floats in the layout below.  Optional outputs (NULL: not stored): pseudo1,
+ *   pseudo2 uint8 [B, H, W]; var1, var2 fp32 [B, H, W] = v1, v2.  A label outside [0, C) enters no term and is counted in
+ *   scalars[UAPS_UCC_S_BAD].  workspace: uaps_ucc_workspace_bytes().
+ * uaps_ucc_bwd: one launch overwrites every row of dz1 and dz2 with d(g_sup sup + g_ps ps) / dz.  g_*: device pointers to one float
+ *   each, NULL = 1.  Neither softmax of a KL pair is detached (the reference detaches the pseudo-labels only).
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_UCC_MAX_BATCH 64
+#define UAPS_UCC_S_CE 0                                     /* ce[4]                                              */
+#define UAPS_UCC_S_DICE 4                                   /* dice[4]                                            */
+#define UAPS_UCC_S_SUP 8
+#define UAPS_UCC_S_PS 9
+#define UAPS_UCC_S_PS1 10
+#define UAPS_UCC_S_PS2 11
+#define UAPS_UCC_S_V1 12                                    /* mean v1                                            */
+#define UAPS_UCC_S_E1 13                                    /* mean exp(-v1)                                      */
+#define UAPS_UCC_S_V2 14
+#define UAPS_UCC_S_E2 15
+#define UAPS_UCC_S_BAD 16                                   /* number of labels outside [0,C) (must be 0); 17..19 reserved */
+#define UAPS_UCC_S_A1(C) 20                                 /* [4][C]  2 / (C (card + eps))                       */
+#define UAPS_UCC_S_A2(C) (20 + 4 * (C))                     /* [4][C]  2 I / (C (card + eps)^2)                   */
+#define UAPS_UCC_S_I(C) (20 + 8 * (C))                      /* [4][C]  Dice intersections                         */
+#define UAPS_UCC_S_CARD(C) (20 + 12 * (C))                  /* [4][C]  Dice cardinalities                         */
+#define UAPS_UCC_S_NSCALARS(C) (20 + 16 * (C))
+int uaps_ucc_cutmix_batch(const float* x_l, const float* x_wk, const float* x_st, const int64_t* y_l, const int32_t* rects_l_host,
+                          const int32_t* rects_u_host, int B, int Cin, int H, int W, float* out, int64_t* y_out, uaps_stream_t stream);
+int uaps_ucc_workspace_bytes(int B, int C, int H, int W, size_t* out_host);
+int uaps_ucc_fwd(const float* z1, const float* z2, const int64_t* labels, int B, int C, int H, int W, float eps, uint8_t* pseudo1,
+                 uint8_t* pseudo2, float* var1, float* var2, float* scalars, void* workspace, size_t workspace_bytes,
+                 uaps_stream_t stream);
+int uaps_ucc_bwd(const float* z1, const float* z2, const int64_t* labels, const float* scalars, const float* g_sup, const float* g_ps,
+                 int B, int C, int H, int W, float* dz1, float* dz2, uaps_stream_t stream);
+
 /* Residual join of the ResNet blocks (utilities/resnet.py:47-50, 88-91): out = relu(a + b) over n floats; the
  * backward of both addends is dx = dout * (out > 0). */
 int uaps_add_relu(const float* a, const float* b, float* out, long n, uaps_stream_t stream);
@@ -853,6 +907,9 @@ int uaps_cat2_h(const uaps_call_hints* hints, const float* a, const float* b, fl
 int uaps_add_relu_h(const uaps_call_hints* hints, const float* a, const float* b, float* out, long n, uaps_stream_t stream);
 int uaps_rot90_batch_h(const uaps_call_hints* hints, const float* x_l, const float* x_u, int B, int Cin, int H, int W, int k, float* out,
                        float* rot_out, uaps_stream_t stream);
+int uaps_ucc_cutmix_batch_h(const uaps_call_hints* hints, const float* x_l, const float* x_wk, const float* x_st, const int64_t* y_l,
+                            const int32_t* rects_l_host, const int32_t* rects_u_host, int B, int Cin, int H, int W, float* out,
+                            int64_t* y_out, uaps_stream_t stream);
 int uaps_pairloss_bwd_h(const uaps_call_hints* hints, const float* const* lab_logits_host, const float* const* un_logits_host,
                         const int64_t* labels, const int64_t* pseudo, const float* sup_scalars, const float* unsup_scalars, float cw1,
                         float cw2, const float* grad_scale, int D, int B, int C, int H, int W, long n_pixels_loss,

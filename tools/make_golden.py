@@ -533,6 +533,115 @@ def g9():
     print(f"g9 seed {seed} near-ties {near}: sup {float(sup_loss):.6f} labeled_cps {float(labeled_cps):.6f} cps {float(cps_loss):.6f}")
 
 
+def g10():
+    """UCC (UCC/UCC_train.py, UCC/UCC_unet.py, UCC/cross_cutmix.py).  (a) the ordered state_dict keys and shapes of the reference's
+    UNet_UCC(3, 4) and its main_seg in eval mode on formula weights (tests/formula_weights.py) for one 1x3x32x32 input (the auxiliary
+    head draws noise in eval mode too: not pinned); (b) the loss block of UCC_train.py:186-246 on fixed random logits z1, z2
+    [6,4,24,20] (rows [:2] labelled, [2:4] weak, [4:] strong): the eight terms from the reference's dice_loss and
+    nn.CrossEntropyLoss() composed as the script does, the variance maps, torch.argmax(softmax) pseudo-labels with their top-2 softmax
+    gaps, sup, ps_1, ps_2, ps and the autograd gradients of sup + cw * ps for cw = 0.07; (c) generate_mix_data and
+    generate_crossmix_data of cross_cutmix.py on a recorded B = 4 batch with the global generators seeded (the seed searched so that
+    both flags occur in both lists).  cross_cutmix imports torchvision.transforms.functional at module level for functions not used
+    here: an empty stand-in module is registered for the import.  The training script imports tensorboardX / cv2 and cannot be
+    imported."""
+    import random
+    import types
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    from formula_weights import formula_state_dict, formula_input
+    import UCC.UCC_unet as R_ucc
+    if "torchvision" not in sys.modules:
+        tv, tvt, tvf = types.ModuleType("torchvision"), types.ModuleType("torchvision.transforms"), types.ModuleType("torchvision.transforms.functional")
+        tv.transforms, tvt.functional = tvt, tvf
+        sys.modules.update({"torchvision": tv, "torchvision.transforms": tvt, "torchvision.transforms.functional": tvf})
+    import UCC.cross_cutmix as R_mix
+    # ---- (a)
+    torch.manual_seed(0)
+    net = R_ucc.UNet_UCC(3, 4)
+    out = {"keys": np.array(list(net.state_dict().keys())), "shapes": np.array([str(tuple(v.shape)) for v in net.state_dict().values()])}
+    net.load_state_dict(formula_state_dict(net.state_dict()))
+    net.eval()
+    x = formula_input((1, 3, 32, 32))
+    with torch.no_grad():
+        main_seg, _ = net(x)
+    out["x"], out["main_seg"] = x.numpy(), main_seg.numpy()
+    # ---- (b)
+    B, C, H, W, cw = 2, 4, 24, 20, 0.07
+    seed = 41
+    while True:
+        rng = np.random.default_rng(seed)
+        z = [torch.tensor((rng.standard_normal((3 * B, C, H, W)) * 2).astype(np.float32), requires_grad=True) for _ in range(2)]
+        soft = [torch.softmax(t.detach()[B:2 * B], dim=1) for t in z]          # the weak rows give the pseudo-labels
+        top2 = [torch.topk(s_, 2, dim=1).values for s_ in soft]
+        near = sum(int(((t2[:, 0] - t2[:, 1]) <= 1e-5).sum()) for t2 in top2)
+        if near <= 1e-4 * 2 * B * H * W:
+            break
+        seed += 1
+    labels_l = torch.tensor(rect_labels(rng, B, C, H, W))
+    outputs1, outputs2 = z[0][:B], z[1][:B]
+    un_outputs1_wk, un_outputs2_wk = z[0][B:2 * B], z[1][B:2 * B]
+    un_outputs1_st, un_outputs2_st = z[0][2 * B:], z[1][2 * B:]
+    un_outputs1_wk_soft = torch.softmax(un_outputs1_wk, dim=1)
+    un_outputs2_wk_soft = torch.softmax(un_outputs2_wk, dim=1)
+    un_outputs2_st_soft = torch.softmax(un_outputs2_st, dim=1)
+    loss_ce_1 = ce_loss(outputs1, labels_l.long())
+    loss_ce_2 = ce_loss(outputs2, labels_l.long())
+    loss_dice_1 = R_dice(labels_l.unsqueeze(1), outputs1)
+    loss_dice_2 = R_dice(labels_l.unsqueeze(1), outputs2)
+    sup_loss_1 = 0.5 * (loss_ce_1 + loss_dice_1)
+    sup_loss_2 = 0.5 * (loss_ce_2 + loss_dice_2)
+    supervised_loss = sup_loss_1 + sup_loss_2
+    variance_1 = torch.sum(kl_distance(log_sm(un_outputs1_wk), un_outputs2_st_soft), dim=1)
+    exp_variance_1 = torch.exp(-variance_1)
+    variance_2 = torch.sum(kl_distance(log_sm(un_outputs1_st), un_outputs2_wk_soft), dim=1)
+    exp_variance_2 = torch.exp(-variance_2)
+    pseudo_1 = torch.argmax(un_outputs2_wk_soft.detach(), dim=1, keepdim=False)
+    pseudo_2 = torch.argmax(un_outputs1_wk_soft.detach(), dim=1, keepdim=False)
+    t2 = (ce_loss(un_outputs1_st, pseudo_1), R_dice(pseudo_1.unsqueeze(1), un_outputs1_st))
+    t3 = (ce_loss(un_outputs2_st, pseudo_2), R_dice(pseudo_2.unsqueeze(1), un_outputs2_st))
+    ps_1_wk = torch.mean(0.5 * (t2[0] + t2[1]) * exp_variance_1) + torch.mean(variance_1)
+    ps_2_st = torch.mean(0.5 * (t3[0] + t3[1]) * exp_variance_2) + torch.mean(variance_2)
+    ps_loss = ps_1_wk + ps_2_st
+    loss = supervised_loss + cw * ps_loss
+    loss.backward()
+    terms = [(loss_ce_1, loss_dice_1), (loss_ce_2, loss_dice_2), t2, t3]
+    out.update(z1=z[0].detach().numpy(), z2=z[1].detach().numpy(), labels=labels_l.numpy().astype(np.int64), cw=np.float64(cw),
+               seed=np.int64(seed), ce=np.array([float(a) for a, _ in terms], dtype=np.float64),
+               dice=np.array([float(b) for _, b in terms], dtype=np.float64), sup=np.float64(float(supervised_loss)),
+               ps=np.float64(float(ps_loss)), ps_1=np.float64(float(ps_1_wk)), ps_2=np.float64(float(ps_2_st)),
+               loss=np.float64(float(loss)), dz1=z[0].grad.numpy(), dz2=z[1].grad.numpy(),
+               variance_1=variance_1.detach().numpy(), variance_2=variance_2.detach().numpy(),
+               pseudo1=pseudo_1.numpy().astype(np.uint8), pseudo2=pseudo_2.numpy().astype(np.uint8),
+               gap1=(top2[1][:, 0] - top2[1][:, 1]).numpy(), gap2=(top2[0][:, 0] - top2[0][:, 1]).numpy())
+    # ---- (c)
+    Bm, Ci, Hm, Wm = 4, 3, 24, 20
+    rng = np.random.default_rng(7)
+    data_l, data_wk, data_st = (torch.tensor(rng.standard_normal((Bm, Ci, Hm, Wm)).astype(np.float32)) for _ in range(3))
+    target = torch.tensor(rect_labels(rng, Bm, 4, Hm, Wm))
+    mseed = 0
+    while True:
+        np.random.seed(mseed); random.seed(mseed)
+        st_np, st_py = np.random.get_state(), random.getstate()
+        flags = []
+        for p in (0.2, 0.3):
+            f = []
+            for _ in range(Bm):
+                R_mix.generate_cutout_mask([Hm, Wm])
+                f.append(random.random() < p)
+            flags.append(f)
+        if all(any(f) and not all(f) for f in flags):
+            break
+        mseed += 1
+    np.random.set_state(st_np); random.setstate(st_py)
+    inputs_l, labels_mix = R_mix.generate_mix_data(data_l, target)
+    new_U1, new_U2 = R_mix.generate_crossmix_data(inputs_l, data_wk, data_st)
+    out.update(mix_x_l=data_l.numpy(), mix_x_wk=data_wk.numpy(), mix_x_st=data_st.numpy(), mix_y_l=target.numpy().astype(np.int64),
+               mix_seed=np.int64(mseed), mix_flags=np.array(flags, dtype=np.int64), mix_out_l=inputs_l.numpy(),
+               mix_out_y=labels_mix.numpy().astype(np.int64), mix_out_wk=new_U1.numpy(), mix_out_st=new_U2.numpy())
+    np.savez_compressed(os.path.join(OUT, "g10_ucc.npz"), **out)
+    print(f"g10 seed {seed} near-ties {near}: sup {float(supervised_loss):.6f} ps_1 {float(ps_1_wk):.6f} ps_2 {float(ps_2_st):.6f}; "
+          f"mix seed {mseed} flags {flags}")
+
+
 def main():
     torch.set_num_threads(4)
     only = sys.argv[1:]                      # e.g. `python tools/make_golden.py g9`: that fixture alone
@@ -558,6 +667,7 @@ def main():
     g7()
     g8()
     g9()
+    g10()
 
 
 if __name__ == "__main__":

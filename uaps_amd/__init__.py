@@ -8,13 +8,14 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   mIoU, mDice, pixel_accuracy, seg_confusion        (utilities/metrics.py)
   softmax_mse_loss, softmax_kl_loss, kl_loss, entropy_map, entropy_minmization   (utilities/losses_1.py, losses_2.py)
   uncertainty_map                                   (UAPS-Testing.ipynb cell 24)
-  sibling.cct_consistency_loss / ucc_pseudo_supervision / uamt_consistency_loss   (CCT_train.py:195-199,
+  sibling.cct_consistency_loss / ucc_pseudo_supervision / uamt_consistency_loss   the composed reference-shaped forms (CCT_train.py:195-199,
                                                     UCC_train.py:213-238, UA_MT_train.py:188-214)
   SegTrainer                                        the base of every trainer: optimizer + schedule, step frame, fit, checkpoints
   UAPSTrainer                                       (UAPS_train.py:109-450 step/optimizer/checkpoint)
   MeanTeacherTrainer, UAMTTrainer, ema_update, mc_consistency   (MT/MT_train.py, UAMT/UA_MT_train.py)
   CCTTrainer, DCTTrainer, cct_consistency, rot_consistency, rot90_batch   (CCT/CCT_train.py, DCT/DCT_train.py)
   CPSTrainer, cps_loss, cps_scalars, UNet_f         (CPS/CPS_train.py, utilities/m_unet.py)
+  UCCTrainer, ucc_loss, ucc_scalars, cutmix_batch, cutmix_rects   (UCC/UCC_train.py, UCC/cross_cutmix.py; net_factory("unet_ucc"))
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -29,6 +30,7 @@ from .trainer import SegTrainer, UAPSTrainer, BaselineTrainer
 from .mean_teacher import MeanTeacherTrainer, UAMTTrainer, ema_update, mc_consistency
 from .cct_dct import CCTTrainer, DCTTrainer, cct_consistency, rot_consistency, rot90_batch
 from .cps import CPSTrainer, cps_loss, cps_scalars
-from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, sibling
+from .ucc import UCCTrainer, ucc_loss, ucc_scalars, cutmix_batch, cutmix_rects
+from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -140,6 +140,10 @@ SIGNATURES = {
     "uaps_cps_workspace_bytes": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_size_t)]),
     "uaps_cps_fwd": (C.c_int, [_PTR] * 3 + [C.c_int] * 5 + [C.c_float] + [_PTR] * 4 + [C.c_size_t, _PTR]),
     "uaps_cps_bwd": (C.c_int, [_PTR] * 7 + [C.c_int] * 5 + [_PTR] * 3),
+    "uaps_ucc_cutmix_batch": (C.c_int, [_PTR] * 6 + [C.c_int] * 4 + [_PTR] * 3),
+    "uaps_ucc_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
+    "uaps_ucc_fwd": (C.c_int, [_PTR] * 3 + [C.c_int] * 4 + [C.c_float] + [_PTR] * 6 + [C.c_size_t, _PTR]),
+    "uaps_ucc_bwd": (C.c_int, [_PTR] * 6 + [C.c_int] * 4 + [_PTR] * 3),
 }
 
 
@@ -148,7 +152,7 @@ SIGNATURES = {
 HINTED = ("uaps_conv_fwd", "uaps_conv_fwd_stats", "uaps_conv_fwd_bn", "uaps_conv_fwd_cat", "uaps_conv_bwd_data", "uaps_conv_bwd_data_cat",
           "uaps_conv_bwd_weight_partial", "uaps_conv_bwd_weight_partial_bn", "uaps_conv_bwd_weight_partial_cat",
           "uaps_bn_act_fwd_train_partials", "uaps_bn_finalize_train", "uaps_bn_act_bwd_grouped", "uaps_bn_act_bwd_grouped_bias",
-          "uaps_bn_act_bwd_apply", "uaps_up_cat_fwd", "uaps_cat2", "uaps_add_relu", "uaps_pairloss_bwd", "uaps_rot90_batch")
+          "uaps_bn_act_bwd_apply", "uaps_up_cat_fwd", "uaps_cat2", "uaps_add_relu", "uaps_pairloss_bwd", "uaps_rot90_batch", "uaps_ucc_cutmix_batch")
 for _n in HINTED:
     SIGNATURES[_n + "_h"] = (SIGNATURES[_n][0], [_PTR] + list(SIGNATURES[_n][1]))
 del _n

@@ -17,8 +17,10 @@
 #include <math.h>
 #include "../../include/uaps_hip.h"
 #include "hints.hpp"
+#include "loss_pixel.hpp"
 
 namespace {
+using namespace uaps::pixel;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxBlocks = 512;                // per row set (labelled / unlabelled)
@@ -37,95 +39,6 @@ __host__ __device__ constexpr int col_ix(int C, int m, int c) { return 5 + 4 * C
 __host__ __device__ constexpr int col_ny(int C, int c) { return 5 + 6 * C + c; }
 __host__ __device__ constexpr int col_np(int C, int m, int c) { return 5 + 7 * C + m * C + c; }
 __host__ __device__ constexpr int n_cols(int C) { return 5 + 9 * C; }
-
-template <int C, int V>
-__device__ __forceinline__ void load_logits(const float* __restrict__ z, long HW, float (&p)[C][V]) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        if constexpr (V == 4) {
-            const float4 t = *reinterpret_cast<const float4*>(z + (long)c * HW);
-            p[c][0] = t.x; p[c][1] = t.y; p[c][2] = t.z; p[c][3] = t.w;
-        } else {
-            p[c][0] = z[(long)c * HW];
-        }
-    }
-}
-
-template <int C, int V>
-__device__ __forceinline__ void store_planes(float* __restrict__ dz, long HW, const float (&g)[C][V]) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        if constexpr (V == 4)
-            *reinterpret_cast<float4*>(dz + (long)c * HW) = make_float4(g[c][0], g[c][1], g[c][2], g[c][3]);
-        else
-            dz[(long)c * HW] = g[c][0];
-    }
-}
-
-// arg-max over the classes of every pixel, the lowest index among equal logits (strict >)
-template <int C, int V>
-__device__ __forceinline__ void argmax_logits(const float (&z)[C][V], int (&am)[V]) {
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-        float best = z[0][v];
-        int idx = 0;
-#pragma unroll
-        for (int c = 1; c < C; ++c)
-            if (z[c][v] > best) { best = z[c][v]; idx = c; }
-        am[v] = idx;
-    }
-}
-
-// z -> softmax(z) in place; lse[v] = log sum exp (z - max) and mx[v] = max, so that log_softmax(z)[c] = z[c] - mx - lse
-template <int C, int V>
-__device__ __forceinline__ void softmax_inplace(float (&z)[C][V], float (&mx)[V], float (&lse)[V]) {
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-        float m = z[0][v];
-#pragma unroll
-        for (int c = 1; c < C; ++c) m = fmaxf(m, z[c][v]);
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) { z[c][v] = expf(z[c][v] - m); s += z[c][v]; }
-#pragma unroll
-        for (int c = 0; c < C; ++c) z[c][v] = z[c][v] / s;
-        mx[v] = m;
-        lse[v] = logf(s);
-    }
-}
-
-// z[t][v] for a per-pixel class t (a select chain: no dynamically indexed registers); 0 when t is outside [0, C)
-template <int C, int V>
-__device__ __forceinline__ float pick(const float (&z)[C][V], int v, int t) {
-    float r = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) r = (t == c) ? z[c][v] : r;
-    return r;
-}
-
-// the ground truth of a pixel group (labelled rows only; -1 elsewhere and for a label outside [0, C)); returns how many were outside
-template <int C, int V>
-__device__ __forceinline__ float load_labels(const long long* __restrict__ labels, long n, bool lab, int (&y)[V]) {
-    float bad = 0.f;
-#pragma unroll
-    for (int v = 0; v < V; ++v) y[v] = -1;
-    if (lab) {
-        long long t[V];
-        if constexpr (V == 4) {
-            const longlong2 t0 = *reinterpret_cast<const longlong2*>(labels + n), t1 = *reinterpret_cast<const longlong2*>(labels + n + 2);
-            t[0] = t0.x; t[1] = t0.y; t[2] = t1.x; t[3] = t1.y;
-        } else {
-            t[0] = labels[n];
-        }
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-            const bool ok = t[v] >= 0 && t[v] < C;
-            y[v] = ok ? (int)t[v] : -1;
-            bad += ok ? 0.f : 1.f;
-        }
-    }
-    return bad;
-}
 
 // where a block's lane item g lives: labelled blocks walk rows [0, B_lab), the others rows [B_lab, N)
 struct Split { long HW; long items_l, items_u; int gl, gu, B_lab; };

@@ -1,0 +1,136 @@
+// Per-pixel device helpers of the pseudo-supervision loss blocks (loss_cps.hip, loss_ucc.hip): a lane holds all C class logits of V
+// consecutive pixels (V = 4: one float4 per class plane, V = 1 otherwise) in registers.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <math.h>
+
+namespace uaps {
+namespace pixel {
+template <int C, int V>
+__device__ __forceinline__ void load_logits(const float* __restrict__ z, long HW, float (&p)[C][V]) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if constexpr (V == 4) {
+            const float4 t = *reinterpret_cast<const float4*>(z + (long)c * HW);
+            p[c][0] = t.x; p[c][1] = t.y; p[c][2] = t.z; p[c][3] = t.w;
+        } else {
+            p[c][0] = z[(long)c * HW];
+        }
+    }
+}
+
+template <int C, int V>
+__device__ __forceinline__ void store_planes(float* __restrict__ dz, long HW, const float (&g)[C][V]) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if constexpr (V == 4)
+            *reinterpret_cast<float4*>(dz + (long)c * HW) = make_float4(g[c][0], g[c][1], g[c][2], g[c][3]);
+        else
+            dz[(long)c * HW] = g[c][0];
+    }
+}
+
+// arg-max over the classes of every pixel, the lowest index among equal logits (strict >)
+template <int C, int V>
+__device__ __forceinline__ void argmax_logits(const float (&z)[C][V], int (&am)[V]) {
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        float best = z[0][v];
+        int idx = 0;
+#pragma unroll
+        for (int c = 1; c < C; ++c)
+            if (z[c][v] > best) { best = z[c][v]; idx = c; }
+        am[v] = idx;
+    }
+}
+
+// z -> softmax(z) in place; lse[v] = log sum exp (z - max) and mx[v] = max, so that log_softmax(z)[c] = z[c] - mx - lse
+template <int C, int V>
+__device__ __forceinline__ void softmax_inplace(float (&z)[C][V], float (&mx)[V], float (&lse)[V]) {
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        float m = z[0][v];
+#pragma unroll
+        for (int c = 1; c < C; ++c) m = fmaxf(m, z[c][v]);
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) { z[c][v] = expf(z[c][v] - m); s += z[c][v]; }
+#pragma unroll
+        for (int c = 0; c < C; ++c) z[c][v] = z[c][v] / s;
+        mx[v] = m;
+        lse[v] = logf(s);
+    }
+}
+
+// z[t][v] for a per-pixel class t (a select chain: no dynamically indexed registers); 0 when t is outside [0, C)
+template <int C, int V>
+__device__ __forceinline__ float pick(const float (&z)[C][V], int v, int t) {
+    float r = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) r = (t == c) ? z[c][v] : r;
+    return r;
+}
+
+// the ground truth of a pixel group (labelled rows only; -1 elsewhere and for a label outside [0, C)); returns how many were outside
+template <int C, int V>
+__device__ __forceinline__ float load_labels(const long long* __restrict__ labels, long n, bool lab, int (&y)[V]) {
+    float bad = 0.f;
+#pragma unroll
+    for (int v = 0; v < V; ++v) y[v] = -1;
+    if (lab) {
+        long long t[V];
+        if constexpr (V == 4) {
+            const longlong2 t0 = *reinterpret_cast<const longlong2*>(labels + n), t1 = *reinterpret_cast<const longlong2*>(labels + n + 2);
+            t[0] = t0.x; t[1] = t0.y; t[2] = t1.x; t[3] = t1.y;
+        } else {
+            t[0] = labels[n];
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const bool ok = t[v] >= 0 && t[v] < C;
+            y[v] = ok ? (int)t[v] : -1;
+            bad += ok ? 0.f : 1.f;
+        }
+    }
+    return bad;
+}
+
+// One CE + Dice term of a pixel group whose logits `p` have been through softmax_inplace (mx, lse from it): t = the target class
+// of every pixel (-1: none, the pixel enters A only), zt = the target class's LOGIT, picked before the softmax.
+//   ce -= log_softmax(z)[t];  A[c] += p[c];  I[c] += p[c] [t = c];  N[c] += [t = c]
+template <int C, int V>
+__device__ __forceinline__ void term_fwd(const float (&p)[C][V], const int (&t)[V], const float (&zt)[V], const float (&mx)[V],
+                                         const float (&lse)[V], float& ce, float (&A)[C], float (&I)[C], float (&N)[C]) {
+#pragma unroll
+    for (int v = 0; v < V; ++v)
+        if (t[v] >= 0) ce -= zt[v] - mx[v] - lse[v];
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            A[c] += p[c][v];
+            I[c] += (t[v] == c) ? p[c][v] : 0.f;
+            N[c] += (t[v] == c) ? 1.f : 0.f;
+        }
+}
+
+// The gradient of w (CE + Dice) of one term at pixel v, ADDED to g: p = softmax(z) of the pixel group, t = the target class (-1:
+// no CE part), a1 / a2 = the term's Dice coefficient rows (2 / (C (card + eps)), 2 I / (C (card + eps)^2)), inv_n = 1 / pixels:
+//   CE:    w inv_n (p - onehot(t))
+//   Dice:  d[c] = w (a2[c] - [t = c] a1[c]),  dz = p (d - <p, d>)
+template <int C, int V>
+__device__ __forceinline__ void term_grad_add(const float (&p)[C][V], int v, int t, float w, float inv_n, const float* __restrict__ a1,
+                                              const float* __restrict__ a2, float (&g)[C]) {
+    float d[C], dot = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        d[c] = w * a2[c] - ((t == c) ? w * a1[c] : 0.f);
+        dot += p[c][v] * d[c];
+    }
+    const float cw = t >= 0 ? w * inv_n : 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) g[c] += p[c][v] * (d[c] - dot) + cw * (p[c][v] - ((t == c) ? 1.f : 0.f));
+}
+}  // namespace pixel
+}  // namespace uaps

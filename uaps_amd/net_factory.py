@@ -17,6 +17,8 @@ def net_factory(net_type="unet_uaps", in_chns=3, class_num=4, n_aux=3):
         net = UNet_UAPS(in_chns=in_chns, class_num=class_num, n_aux=n_aux)
     elif net_type == "unet_cct":                  # CCT/net_factory.py: UNet_CCT = UNet_UAPS with the aux Dropout at p = 0.3
         net = UNet_UAPS(in_chns=in_chns, class_num=class_num, n_aux=3, aux_dropout_p=0.3)
+    elif net_type == "unet_ucc":                  # UCC/UCC_unet.py:245-270: main_decoder + aux_decoder1 on FeatureNoise features
+        net = UNet_UAPS(in_chns=in_chns, class_num=class_num, n_aux=1)
     elif net_type in ("resnet50_uaps", "resnet101_uaps", "resnet152_uaps"):     # not in the reference: BASELINE.json configs[4]
         net = ResUAPS(in_chns=in_chns, class_num=class_num, n_aux=n_aux, backbone=net_type.split("_")[0])
     else:

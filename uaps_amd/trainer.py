@@ -246,8 +246,7 @@ class SegTrainer:
             kept = []
             for _ in range(1, int(iter_per_epoch)):
                 (x_l, y_l), u = next(semi)
-                x_u = u[0] if isinstance(u, (tuple, list)) else u
-                res = self.train_step(x_l.to(self.device), y_l.to(self.device), x_u.to(self.device))
+                res = self.train_step(x_l.to(self.device), y_l.to(self.device), *(t.to(self.device) for t in self._unlabeled_inputs(u)))
                 kept.append(torch.stack([res[k].float() for k in keys]))
             rec: Dict = {"epoch": epoch, "iter_num": self.iter_num}
             rec.update(zip(("lr" + s for s in sfx), self.learning_rates()))
@@ -272,6 +271,11 @@ class SegTrainer:
             if log is not None:
                 log(rec)
         return history
+
+    def _unlabeled_inputs(self, u):
+        """What `fit` hands to `train_step` behind the labelled pair, from one item of `unlabeled_batches`: the image batch of an
+        (x, y) item, the labels ignored (:166).  A trainer whose step takes more than one unlabelled view overrides it."""
+        return (u[0] if isinstance(u, (tuple, list)) else u,)
 
     def _fit_begin(self, best_dice, checkpoint_path):
         """Start of fit(): the best mDice to beat (default 0), a fresh patience count; returns every network's checkpoint path."""

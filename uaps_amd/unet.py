@@ -361,6 +361,17 @@ class UNet_UAPS(nn.Module):
         with fused.stat_groups(2):
             return self.forward(fused.cat_batches(x_a, x_b), perturbations, _groups=2)
 
+    def forward_groups(self, batch, groups: int, perturbations=None):
+        """`forward_pair` for G = `groups` forwards: `batch` holds G equal batches one after the other (e.g. the output of
+        ucc.cutmix_batch, G = 3) and runs as ONE pass under stat_groups(G) -- train-mode BatchNorm statistics, the successive
+        running-statistics updates, the FeatureNoise tensor and the FeatureDropout threshold are per group.  Returns D logit tensors
+        [G B, class_num, H, W].  GPU only; the fused fan-out takes G <= 4."""
+        G = int(groups)
+        if G < 1 or batch.shape[0] % G:
+            raise ValueError(f"forward_groups: a joined batch of {batch.shape[0]} images is not {groups} equal groups")
+        with fused.stat_groups(G):
+            return self.forward(batch, perturbations, _groups=G)
+
     def forward(self, x, perturbations=None, _groups: int = 1):
         """`perturbations`: optional list (one entry per auxiliary decoder) of callables
         feats -> feats replacing the random draws (parity tests inject recorded draws here)."""

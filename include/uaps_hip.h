@@ -797,6 +797,76 @@ int uaps_ucc_fwd(const float* z1, const float* z2, const int64_t* labels, int B,
 int uaps_ucc_bwd(const float* z1, const float* z2, const int64_t* labels, const float* scalars, const float* g_sup, const float* g_ps,
                  int B, int C, int H, int W, float* dz1, float* dz2, uaps_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The supervised loss family (utilities/pytorch_losses.py: ce_loss :31-51, dice_loss :54-89, jaccard_loss :92-128, tversky_loss
+ * :131-175; utilities/losses_1.py: FocalLoss :63-97, DiceLoss :100-136): csrc/loss_seg.hip.  z: fp32 logits [B, C, H, W] (contiguous),
+ * labels int64 [B, H, W]; C in [2, UAPS_MAX_CLASSES] (UAPS_ERANGE), every tensor below 2 GiB (UAPS_ERANGE).
+ * With p = softmax(z) over the classes, y the label, nll = -log p_y, valid = (y != ignore_index) and the sums over the valid pixels
+ *   A_c = sum p_c,  I_c = sum p_c [y = c],  N_c = #[y = c],  Z_c = sum p_c^2
+ * the terms are
+ *   ce      = sum w_y nll / sum w_y                      w = class_weight (torch's weight + ignore_index mean; 0/0 = NaN when every
+ *                                                        pixel is ignored, as in torch)
+ *   focal   = sum a_y (1 - p_y)^gamma nll / n_valid      a = focal_alpha; focal_mean == 0: the sum.  (1 - p_y)^gamma carries no
+ *                                                        gradient (the reference detaches p_t, losses_1.py:85)
+ *   dice    = 1 - mean_c 2 I_c / (A_c + N_c + eps)
+ *   jaccard = 1 - mean_c I_c / (A_c + N_c - I_c + eps)
+ *   tversky = 1 - mean_c I_c / (I_c + alpha (A_c - I_c) + beta (N_c - I_c) + eps)
+ *   dice_sq = (1 / C) sum_c v_c (1 - (2 I_c + smooth) / (Z_c + N_c + smooth))        v = dice_sq_weight; losses_1.DiceLoss with
+ *                                                        softmax=True has smooth = 1e-5
+ *   loss    = sum over the terms selected in `terms` of coef[t] * term_t               (t = the bit's index)
+ * A defined extension: a pixel whose label equals ignore_index enters NO term (the reference's region losses raise on such a label,
+ * torch.eye(C)[true] indexes out of range; its FocalLoss has no ignore_index).  With no ignored pixel every term equals the
+ * reference's.  A label outside [0, C) that is not ignore_index enters no term either and is counted in scalars[UAPS_SEG_S_BAD].
+ * uaps_segloss_params is passed by value into the kernels: nothing is copied to the device and nothing waits for it.
+ * uaps_segloss_fwd: one pass over z (each logit read once) + one finalize launch (block partial sums in the workspace, added in
+ *   double in a fixed order: deterministic).  scalars: UAPS_SEG_S_NSCALARS(C) floats in the layout below; a term that is not selected
+ *   is stored as 0 (Z_c is accumulated only when dice_sq is selected).
+ * uaps_segloss_bwd: one launch overwrites all of dz with grad[0] * d loss / dz (grad: device pointer to one float, NULL = 1, read on
+ *   the device); dz = 0 at ignored and at out-of-range pixels.  prm and scalars: what the forward got and wrote for the same tensors.
+ * Errors (nothing is launched): UAPS_EINVAL null pointer, non-positive dimension, terms == 0 or a bit outside UAPS_SEG_ALL,
+ *   struct_size below the first version's; UAPS_ERANGE; UAPS_EWORKSPACE.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_SEG_CE 1u
+#define UAPS_SEG_FOCAL 2u
+#define UAPS_SEG_DICE 4u
+#define UAPS_SEG_JACCARD 8u
+#define UAPS_SEG_TVERSKY 16u
+#define UAPS_SEG_DICE_SQ 32u
+#define UAPS_SEG_ALL 63u
+#define UAPS_SEG_NTERMS 6
+typedef struct uaps_segloss_params {
+    uint32_t struct_size;                        /* sizeof(uaps_segloss_params) of the caller's header; fields are only ever appended */
+    uint32_t terms;                              /* bit mask UAPS_SEG_CE | _FOCAL | _DICE | _JACCARD | _TVERSKY | _DICE_SQ */
+    float coef[UAPS_SEG_NTERMS];                 /* coefficient of term t = bit index                                       */
+    float class_weight[UAPS_MAX_CLASSES];        /* CE                                                                      */
+    float focal_alpha[UAPS_MAX_CLASSES];
+    float focal_gamma;
+    int focal_mean;                              /* non-zero: divide by the number of valid pixels (size_average)           */
+    float dice_sq_weight[UAPS_MAX_CLASSES];
+    float tversky_alpha, tversky_beta, eps, smooth;
+    int64_t ignore_index;                        /* a value no label takes (e.g. INT64_MIN) = nothing ignored               */
+} uaps_segloss_params;
+#define UAPS_SEG_S_TERM 0                                   /* term[6]: ce, focal, dice, jaccard, tversky, dice_sq  */
+#define UAPS_SEG_S_LOSS 6
+#define UAPS_SEG_S_BAD 7                                    /* labels outside [0,C) and != ignore_index (must be 0) */
+#define UAPS_SEG_S_NVALID 8                                 /* pixels that entered the terms                        */
+#define UAPS_SEG_S_WSUM 9                                   /* sum w_y (0 unless ce is selected)                    */
+#define UAPS_SEG_S_KCE 10                                   /* coef_ce / sum w_y               (0: not selected)    */
+#define UAPS_SEG_S_KFOCAL 11                                /* coef_focal / n_valid, or coef_focal for the sum      */
+#define UAPS_SEG_S_A(C) 16                                  /* [C]  sum p_c                     12..15 reserved     */
+#define UAPS_SEG_S_I(C) (16 + (C))                          /* [C]  sum p_c [y = c]                                 */
+#define UAPS_SEG_S_N(C) (16 + 2 * (C))                      /* [C]  #[y = c]                                        */
+#define UAPS_SEG_S_Z(C) (16 + 3 * (C))                      /* [C]  sum p_c^2                                       */
+#define UAPS_SEG_S_GA(C) (16 + 4 * (C))                     /* [C]  d loss / d A_c     backward: d loss / d p_c =   */
+#define UAPS_SEG_S_GI(C) (16 + 5 * (C))                     /* [C]  d loss / d I_c       GA_c + [y = c] GI_c        */
+#define UAPS_SEG_S_GZ(C) (16 + 6 * (C))                     /* [C]  d loss / d Z_c       + 2 p_c GZ_c               */
+#define UAPS_SEG_S_NSCALARS(C) (16 + 7 * (C))
+int uaps_segloss_workspace_bytes(int B, int C, int H, int W, size_t* out_host);
+int uaps_segloss_fwd(const float* z, const int64_t* labels, const uaps_segloss_params* prm, int B, int C, int H, int W, float* scalars,
+                     void* workspace, size_t workspace_bytes, uaps_stream_t stream);
+int uaps_segloss_bwd(const float* z, const int64_t* labels, const uaps_segloss_params* prm, const float* scalars, const float* grad,
+                     int B, int C, int H, int W, float* dz, uaps_stream_t stream);
+
 /* Residual join of the ResNet blocks (utilities/resnet.py:47-50, 88-91): out = relu(a + b) over n floats; the
  * backward of both addends is dx = dout * (out > 0). */
 int uaps_add_relu(const float* a, const float* b, float* out, long n, uaps_stream_t stream);

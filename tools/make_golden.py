@@ -642,6 +642,53 @@ def g10():
           f"mix seed {mseed} flags {flags}")
 
 
+def make_g11_seglosses():
+    """The supervised loss family: utilities/pytorch_losses.py ce_loss (:31-51), jaccard_loss (:92-128), tversky_loss (:131-175) and
+    utilities/losses_1.py FocalLoss (:63-97), DiceLoss (:100-136), the imported functions themselves, on three cases
+    (B,C,H,W) = (2,4,24,20), (2,2,15,13), (1,7,16,16) of fp32 logits ~ N(0, 2^2).  Per case (prefix c0_, c1_, c2_): logits, labels;
+    ce_loss on a label copy with a strip of 255s and a non-uniform fp32 weight vector; FocalLoss(gamma 2 and 1.5, list alpha);
+    tversky_loss(0.3, 0.7); DiceLoss(C)(..., weight, softmax=True); every value (float64 of the fp32 result) and its autograd gradient;
+    FocalLoss(gamma 2, alpha None, size_average=False): the value only."""
+    from utilities.pytorch_losses import ce_loss as R_ce, jaccard_loss as R_jacc, tversky_loss as R_tv
+    out = {}
+    for i, (B, C, H, W) in enumerate(((2, 4, 24, 20), (2, 2, 15, 13), (1, 7, 16, 16))):
+        rng = np.random.default_rng(110 + i)
+        z0 = (rng.standard_normal((B, C, H, W)) * 2).astype(np.float32)
+        labels = rect_labels(rng, B, C, H, W).astype(np.int64)
+        labels_ign = labels.copy()
+        labels_ign[:, 2:5, :] = 255
+        ce_w = (0.5 + rng.random(C) * 1.5).astype(np.float32)
+        alpha = (0.25 + rng.random(C) * 0.75).astype(np.float32)
+        dsq_w = (0.5 + rng.random(C)).astype(np.float32)
+        y = torch.tensor(labels)
+        cases = {
+            "ce": lambda z: R_ce(torch.tensor(labels_ign), z, torch.tensor(ce_w), ignore=255),
+            "jaccard": lambda z: R_jacc(y.unsqueeze(1), z),
+            "tversky": lambda z: R_tv(y.unsqueeze(1), z, 0.3, 0.7),
+            "focal_g2": lambda z: R_l1.FocalLoss(gamma=2, alpha=[float(a) for a in alpha])(z, y),
+            "focal_g15": lambda z: R_l1.FocalLoss(gamma=1.5, alpha=[float(a) for a in alpha])(z, y),
+            "focal_sum": lambda z: R_l1.FocalLoss(gamma=2, alpha=None, size_average=False)(z, y),
+            "dice_sq": lambda z: R_l1.DiceLoss(C)(z, y.unsqueeze(1), weight=[float(a) for a in dsq_w], softmax=True),
+        }
+        pre = f"c{i}_"
+        out.update({pre + "logits": z0, pre + "labels": labels.astype(np.uint8), pre + "labels_ign": labels_ign.astype(np.uint8),
+                    pre + "ce_w": ce_w, pre + "alpha": alpha, pre + "dsq_w": dsq_w})
+        line = []
+        for name, fn in cases.items():
+            z = torch.tensor(z0, requires_grad=True)
+            v = fn(z)
+            v.backward()
+            v = v.detach()
+            out[pre + name] = np.float64(float(v))
+            if name != "focal_sum":                          # (its gradient is n_pixels times focal's with alpha = 1: the value pins the form)
+                out[pre + "d" + name] = z.grad.numpy().copy()
+            line.append(f"{name} {float(v):.6f}")
+        print(f"g11 case {i} {(B, C, H, W)}: " + " ".join(line))
+    path = os.path.join(OUT, "g11_seglosses.npz")
+    np.savez_compressed(path, **out)
+    print(f"g11: {os.path.getsize(path)} bytes")
+
+
 def main():
     torch.set_num_threads(4)
     only = sys.argv[1:]                      # e.g. `python tools/make_golden.py g9`: that fixture alone
@@ -668,6 +715,7 @@ def main():
     g8()
     g9()
     g10()
+    make_g11_seglosses()
 
 
 if __name__ == "__main__":

@@ -16,6 +16,8 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   CCTTrainer, DCTTrainer, cct_consistency, rot_consistency, rot90_batch   (CCT/CCT_train.py, DCT/DCT_train.py)
   CPSTrainer, cps_loss, cps_scalars, UNet_f         (CPS/CPS_train.py, utilities/m_unet.py)
   UCCTrainer, ucc_loss, ucc_scalars, cutmix_batch, cutmix_rects   (UCC/UCC_train.py, UCC/cross_cutmix.py; net_factory("unet_ucc"))
+  SegLoss, seg_scalars, jaccard_loss, tversky_loss, FocalLoss, DiceLoss, seg_losses.ce_loss   the supervised loss family
+                                                    (utilities/pytorch_losses.py, losses_1.py); BaselineTrainer(loss=SegLoss(...))
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -31,6 +33,7 @@ from .mean_teacher import MeanTeacherTrainer, UAMTTrainer, ema_update, mc_consis
 from .cct_dct import CCTTrainer, DCTTrainer, cct_consistency, rot_consistency, rot90_batch
 from .cps import CPSTrainer, cps_loss, cps_scalars
 from .ucc import UCCTrainer, ucc_loss, ucc_scalars, cutmix_batch, cutmix_rects
-from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, sibling, ucc
+from .seg_losses import SegLoss, seg_scalars, jaccard_loss, tversky_loss, FocalLoss, DiceLoss
+from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

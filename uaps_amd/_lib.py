@@ -144,6 +144,9 @@ SIGNATURES = {
     "uaps_ucc_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
     "uaps_ucc_fwd": (C.c_int, [_PTR] * 3 + [C.c_int] * 4 + [C.c_float] + [_PTR] * 6 + [C.c_size_t, _PTR]),
     "uaps_ucc_bwd": (C.c_int, [_PTR] * 6 + [C.c_int] * 4 + [_PTR] * 3),
+    "uaps_segloss_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
+    "uaps_segloss_fwd": (C.c_int, [_PTR] * 3 + [C.c_int] * 4 + [_PTR, _PTR, C.c_size_t, _PTR]),
+    "uaps_segloss_bwd": (C.c_int, [_PTR] * 5 + [C.c_int] * 4 + [_PTR, _PTR]),
 }
 
 
@@ -264,6 +267,22 @@ class ConvCall(C.Structure):
                 ("w_packed", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("y2", C.c_void_p), ("y_grad", C.c_void_p),
                 ("stats", C.c_void_p), ("xf", C.c_void_p), ("xf_slope", C.c_float), ("xf_groups", C.c_int), ("want_bias", C.c_int),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p), ("hints", CallHints)]
+
+
+SEG_NTERMS, SEG_MAX_CLASSES = 6, 8      # UAPS_SEG_NTERMS, UAPS_MAX_CLASSES
+
+
+def seg_nscalars(Cc: int) -> int:
+    """UAPS_SEG_S_NSCALARS(C) (include/uaps_hip.h)."""
+    return 16 + 7 * Cc
+
+
+class SegLossParams(C.Structure):
+    """uaps_segloss_params (include/uaps_hip.h): passed by value into the kernels of uaps_segloss_fwd / _bwd."""
+    _fields_ = [("struct_size", C.c_uint32), ("terms", C.c_uint32), ("coef", C.c_float * SEG_NTERMS),
+                ("class_weight", C.c_float * SEG_MAX_CLASSES), ("focal_alpha", C.c_float * SEG_MAX_CLASSES), ("focal_gamma", C.c_float),
+                ("focal_mean", C.c_int), ("dice_sq_weight", C.c_float * SEG_MAX_CLASSES), ("tversky_alpha", C.c_float),
+                ("tversky_beta", C.c_float), ("eps", C.c_float), ("smooth", C.c_float), ("ignore_index", C.c_int64)]
 
 
 def mk_hints(bounds=(), out_amax=None, stats=None, residual=None, dyt=None, bsum=None):

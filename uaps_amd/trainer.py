@@ -467,15 +467,28 @@ class BaselineTrainer(SegTrainer):
     """The supervised baseline of BASELINE.json configs[0] (baseline/baseline_train.py:100-173): a single-decoder
     U-Net (`net_factory("unet")`), loss = 0.5 * (dice_loss + CrossEntropy) on the labelled batch only, Adam(lr) and
     ReduceLROnPlateau(max, min_lr 1e-7, patience 40) (:102-105).  It is the D = 1 case of the same kernels: no
-    perturbations, no mixing, no unlabelled branch."""
+    perturbations, no mixing, no unlabelled branch.
+
+    `loss`: None keeps that criterion; a `seg_losses.SegLoss` replaces it (class-weighted CE, focal, Jaccard, Tversky, ... for
+    imbalanced defect data: csrc/loss_seg.hip).  The step then returns "loss", one entry per selected term (these are the instance's
+    `log_keys`) and "bad_labels", the number of labels outside [0, C) that are not the criterion's ignore index (a device scalar, must
+    be 0).  Checkpoints do not hold the criterion: build the resuming trainer with the same one."""
 
     log_keys, weight_keys = ("loss", "ce", "dice"), ()       # (no consistency term)
 
     def __init__(self, model: torch.nn.Module, base_lr: float = 1e-3, seed: int = 1337, overlap_comm: bool = True,
-                 track_metrics: bool = True):
+                 track_metrics: bool = True, loss=None):
         super().__init__(model, base_lr=base_lr, seed=seed, overlap_comm=overlap_comm, track_metrics=track_metrics)
+        self.loss = loss
+        if loss is not None:
+            from . import seg_losses
+            if not isinstance(loss, seg_losses.SegLoss):
+                raise TypeError(f"BaselineTrainer: loss must be a seg_losses.SegLoss or None, got {type(loss).__name__}")
+            self.log_keys = ("loss",) + tuple(loss.term_names)
 
     def train_step(self, x_l: torch.Tensor, y_l: torch.Tensor, x_u=None, w=None) -> Dict[str, torch.Tensor]:
+        if self.loss is not None:
+            return self._train_step_segloss(x_l, y_l)
         with self._step() as backward:
             out = self.model(x_l)                                                 # baseline_train.py:158
             main = out[0] if isinstance(out, (tuple, list)) else out
@@ -484,6 +497,18 @@ class BaselineTrainer(SegTrainer):
         self._count(main, y_l)                                                    # :181-182
         sc = losses.sup_scalars(s.scalars, 1, main.shape[1])
         self.last = {"loss": s.loss.detach(), "ce": sc["ce"][0], "dice": sc["dice"][0]}
+        return self.last
+
+    def _train_step_segloss(self, x_l: torch.Tensor, y_l: torch.Tensor) -> Dict[str, torch.Tensor]:
+        from . import seg_losses
+        with self._step() as backward:
+            out = self.model(x_l)
+            main = out[0] if isinstance(out, (tuple, list)) else out
+            s = self.loss(main, y_l)
+            backward(s.loss)
+        self._count(main, y_l)
+        sc = seg_losses.seg_scalars(s.scalars, main.shape[1])
+        self.last = {"loss": s.loss.detach(), **{k: sc[k] for k in self.loss.term_names}, "bad_labels": sc["bad"]}
         return self.last
 
 

@@ -867,6 +867,84 @@ int uaps_segloss_fwd(const float* z, const int64_t* labels, const uaps_segloss_p
 int uaps_segloss_bwd(const float* z, const int64_t* labels, const uaps_segloss_params* prm, const float* scalars, const float* grad,
                      int B, int C, int H, int W, float* dz, uaps_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * One-channel sigmoid (binary) heads (utilities/losses_2.py: FocalLoss :7-26, JaccardLoss, DiceLoss, BCEJaccardLoss, BCEDiceLoss,
+ * iou :108-139, f_score :145-180; utilities/pytorch_losses.py: bce_loss :9-28 and the num_classes == 1 branches of dice_loss :70-79,
+ * jaccard_loss :108-117, tversky_loss :153-162; utilities/losses_1.py: the sigmoid branches of softmax_mse_loss / softmax_kl_loss):
+ * csrc/loss_binary.hip.  z: fp32 logits [B, 1, H, W] (contiguous, below 2 GiB: UAPS_ERANGE).  target: int64 labels [B, H, W] in {0, 1}
+ * (target_float == 0) or a float32 soft target in [0, 1] of the logits' shape (target_float != 0; not range-checked).
+ * With p = sigmoid(z), g the target, sp = log1p(exp(-|z|)), over the elements that enter (all of a float target; the labels in {0, 1}):
+ *   l0 = max(z, 0) - z g + sp                                      F.binary_cross_entropy_with_logits
+ *   l  = (1 - g) z + (1 + (w - 1) g) (sp + max(-z, 0))             the same with pos_weight w (has_pos_weight != 0), else l = l0
+ *   n = #elements,  P = sum p,  G = sum g,  I = sum g p
+ *   bce      = sum l / n
+ *   focal    = alpha sum (1 - e^{-l0})^gamma l0 / n                focal_mean == 0: the sum.  e^{-l0} carries its gradient (losses_2.py:20
+ *                                                                  does not detach it)
+ *   jaccard  = 1 - (I + eps) / (G + P - I + eps)                   losses_2.JaccardLoss
+ *   fscore   = 1 - ((1 + b2) I + eps) / ((1 + b2) I + b2 (G - I) + (P - I) + eps),  b2 = beta^2        losses_2.DiceLoss at beta = 1
+ *   dice2, jaccard2, tversky2 = the multi-class formulas of uaps_segloss_* averaged over the two channels [pos, neg] with
+ *                              I_neg = n - P - G + I,  A_neg = n - P,  N_neg = n - G      (pytorch_losses.py, num_classes == 1)
+ *   loss     = sum over the selected terms of coef[t] * term_t     (t = the bit's index)
+ * A label outside {0, 1} enters no term and is counted in scalars[UAPS_BIN_S_BAD]; dz is 0 there.  If no label is in range
+ *   (n == 0), bce and focal are 0 (not 0 / 0), the region terms are their formulas at all-zero sums, and dz is 0 everywhere.
+ * uaps_binloss_fwd: one pass over z + one finalize launch (block partial sums in the workspace, added in double in a fixed order:
+ *   deterministic).  scalars: UAPS_BIN_S_NSCALARS floats; a term that is not selected is stored as 0.
+ * uaps_binloss_bwd: one launch overwrites dz with grad[0] * d loss / dz =
+ *   grad [k_bce ((1 + (w - 1) g) p - w g) + k_focal d focal / dz + p (1 - p) (gP + g gI)]   (grad: device pointer to one float, NULL = 1).
+ * Errors (nothing is launched): UAPS_EINVAL null pointer, non-positive dimension, terms == 0 or a bit outside UAPS_BIN_ALL, struct_size
+ *   below the first version's; UAPS_ERANGE at 2 GiB; UAPS_EWORKSPACE.
+ * uaps_sigmoid_mse_fwd / _bwd: out[i] = (sigmoid(a) - sigmoid(b))^2 over n floats; da = g_map 2 (sigmoid(a) - sigmoid(b)) p_a (1 - p_a).
+ * uaps_sigmoid_kl_fwd / _bwd: out_mean = mean t (log t - log sigmoid(a)), t = sigmoid(b), log sigmoid(x) = -softplus(-x) (F.kl_div,
+ *   reduction "mean"); da = -grad t (1 - sigmoid(a)) / n.  The gradient goes to a only.  Workspace: uaps_binloss_workspace_bytes.
+ * uaps_bin_confusion: counts[2 t + p] (int64 [2][2], overwritten, exact), p = sigmoid(z) > threshold evaluated as
+ *   z > (float) logit(threshold), 0 < threshold < 1 (UAPS_EINVAL otherwise); a label outside {0, 1} is not counted.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_BIN_BCE 1u
+#define UAPS_BIN_FOCAL 2u
+#define UAPS_BIN_JACCARD 4u
+#define UAPS_BIN_FSCORE 8u
+#define UAPS_BIN_DICE2 16u
+#define UAPS_BIN_JACCARD2 32u
+#define UAPS_BIN_TVERSKY2 64u
+#define UAPS_BIN_ALL 127u
+#define UAPS_BIN_NTERMS 7
+typedef struct uaps_binloss_params {
+    uint32_t struct_size;                        /* sizeof(uaps_binloss_params) of the caller's header; fields are only ever appended */
+    uint32_t terms;                              /* bit mask UAPS_BIN_*                                                      */
+    float coef[UAPS_BIN_NTERMS];                 /* coefficient of term t = bit index                                        */
+    uint32_t target_float;                       /* 0: int64 labels [B,H,W]; non-zero: float32 soft target                   */
+    uint32_t has_pos_weight;                     /* non-zero: bce uses pos_weight                                            */
+    float pos_weight;
+    float focal_alpha, focal_gamma;
+    int focal_mean;                              /* non-zero: divide by n (reduce=True)                                      */
+    float beta;                                  /* fscore                                                                   */
+    float tversky_alpha, tversky_beta, eps;
+} uaps_binloss_params;
+#define UAPS_BIN_S_TERM 0                        /* term[7]: bce, focal, jaccard, fscore, dice2, jaccard2, tversky2          */
+#define UAPS_BIN_S_LOSS 7
+#define UAPS_BIN_S_BAD 8                         /* labels outside {0, 1} (must be 0)                                        */
+#define UAPS_BIN_S_N 9                           /* elements that entered the terms                                          */
+#define UAPS_BIN_S_P 10                          /* sum p                                                                    */
+#define UAPS_BIN_S_G 11                          /* sum g                                                                    */
+#define UAPS_BIN_S_I 12                          /* sum g p                                                                  */
+#define UAPS_BIN_S_GP 13                         /* d loss / dP of the region terms                                          */
+#define UAPS_BIN_S_GI 14                         /* d loss / dI                                                              */
+#define UAPS_BIN_S_KBCE 15                       /* coef_bce / n                        (0: not selected)                    */
+#define UAPS_BIN_S_KFOCAL 16                     /* coef_focal alpha / n, or coef_focal alpha for the sum                    */
+#define UAPS_BIN_S_NSCALARS 24                   /* 17..23 reserved (stored as 0)                                            */
+int uaps_binloss_workspace_bytes(int B, int H, int W, size_t* out_host);
+int uaps_binloss_fwd(const float* z, const void* target, const uaps_binloss_params* prm, int B, int H, int W, float* scalars,
+                     void* workspace, size_t workspace_bytes, uaps_stream_t stream);
+int uaps_binloss_bwd(const float* z, const void* target, const uaps_binloss_params* prm, const float* scalars, const float* grad,
+                     int B, int H, int W, float* dz, uaps_stream_t stream);
+int uaps_sigmoid_mse_fwd(const float* a, const float* b, long n, float* out, uaps_stream_t stream);
+int uaps_sigmoid_mse_bwd(const float* a, const float* b, const float* g_map, long n, float* da, uaps_stream_t stream);
+int uaps_sigmoid_kl_fwd(const float* a, const float* b, long n, float* out_mean, void* workspace, size_t workspace_bytes,
+                        uaps_stream_t stream);
+int uaps_sigmoid_kl_bwd(const float* a, const float* b, const float* grad, long n, float* da, uaps_stream_t stream);
+int uaps_bin_confusion(const float* z, const int64_t* labels, int B, int H, int W, double threshold, int64_t* counts,
+                       uaps_stream_t stream);
+
 /* Residual join of the ResNet blocks (utilities/resnet.py:47-50, 88-91): out = relu(a + b) over n floats; the
  * backward of both addends is dx = dout * (out > 0). */
 int uaps_add_relu(const float* a, const float* b, float* out, long n, uaps_stream_t stream);

@@ -689,6 +689,101 @@ def make_g11_seglosses():
     print(f"g11: {os.path.getsize(path)} bytes")
 
 
+def make_g12_binary():
+    """The binary (one-channel sigmoid) family: utilities/losses_2.py FocalLoss, JaccardLoss, DiceLoss, BCEJaccardLoss, BCEDiceLoss,
+    BCEFocalLoss, iou, f_score; utilities/pytorch_losses.py bce_loss and the num_classes == 1 branches of dice_loss, jaccard_loss,
+    tversky_loss; utilities/losses_1.py softmax_mse_loss / softmax_kl_loss with sigmoid=True -- the imported functions themselves, on
+    three cases of fp32 logits [2,1,24,20] ~ N(0, 2^2): c0 int labels (bce also with pos_weight = 3: "bce_pw"), c1 a soft float target,
+    c2 an all-background target.  Per case: logits, target, every loss value (float64 of the fp32 result), iou / f_score at threshold
+    None and 0.5; c0 also the sigmoid MSE map, its mean and the KL value against a second logit tensor.  The pytorch_losses region
+    forms index torch.eye with the labels, so they are recorded for the integer-label cases only.
+    Gradients (fp32, 3.8 KB each, incompressible) are what the file's size is made of; to stay below 100 KB they are kept for every
+    plain loss of c0, for bce / focal / jaccard / dice of c1 and for the region terms eps decides in c2 (jaccard, dice); the
+    composite losses (bce_jaccard, bce_dice, bce_focal) are sums of recorded terms: their values pin the coefficients.
+    FocalLoss: the installed torch rejects the reference's deprecated `reduce=False` keyword of F.binary_cross_entropy_with_logits, so
+    the imported FocalLoss.forward runs with losses_2's `F` wrapped to spell that keyword reduction="none" -- the same per-element
+    values."""
+    from utilities import pytorch_losses as R_pl
+    import torch.nn.functional as F
+
+    class _F:                                       # losses_2's `F` with reduce=False spelled as today's reduction="none"
+        def __getattr__(self, name):
+            fn = getattr(F, name)
+            if name not in ("binary_cross_entropy_with_logits", "binary_cross_entropy"):
+                return fn
+
+            def call(*a, reduce=None, **k):
+                if reduce is False:
+                    k["reduction"] = "none"
+                return fn(*a, **k)
+            return call
+    R_l2.F = _F()
+    out = {}
+    B, H, W = 2, 24, 20
+    keep_grads = {"int": None, "soft": ("bce", "focal", "jaccard", "dice"), "background": ("jaccard", "dice")}
+    for i, kind in enumerate(("int", "soft", "background")):
+        rng = np.random.default_rng(120 + i)
+        z0 = (rng.standard_normal((B, 1, H, W)) * 2).astype(np.float32)
+        zb = (rng.standard_normal((B, 1, H, W)) * 2).astype(np.float32)
+        if kind == "soft":
+            tgt = rng.random((B, 1, H, W)).astype(np.float32)
+        elif kind == "background":
+            tgt = np.zeros((B, 1, H, W), dtype=np.int64)
+        else:
+            tgt = (rect_labels(rng, B, 2, H, W) > 0).astype(np.int64).reshape(B, 1, H, W)
+        is_int = tgt.dtype == np.int64
+        t_int = torch.tensor(tgt) if is_int else None
+        t_f = torch.tensor(tgt.astype(np.float32))
+        cases = {
+            "bce": lambda z: R_pl.bce_loss(t_f, z),
+            "focal": lambda z: R_l2.FocalLoss(logits=True)(z, t_f),
+            "focal_g15": lambda z: R_l2.FocalLoss(alpha=0.6, gamma=1.5, logits=True)(z, t_f),
+            "jaccard": lambda z: R_l2.JaccardLoss()(z, t_f),
+            "dice": lambda z: R_l2.DiceLoss()(z, t_f),
+            "bce_jaccard": lambda z: R_l2.BCEJaccardLoss()(z, t_f),
+            "bce_dice": lambda z: R_l2.BCEDiceLoss()(z, t_f),
+            "bce_focal": lambda z: R_l2.BCEFocalLoss()(z, t_f),
+        }
+        if kind == "int":
+            cases.update({
+                "bce_pw": lambda z: R_pl.bce_loss(t_f, z, pos_weight=torch.tensor(3.0)),
+                "mse_mean": lambda z: R_l1.softmax_mse_loss(z, torch.tensor(zb), sigmoid=True).mean(),
+                "kl": lambda z: R_l1.softmax_kl_loss(z, torch.tensor(zb), sigmoid=True),
+            })
+        if is_int:
+            cases.update({
+                "dice2": lambda z: R_pl.dice_loss(t_int, z),
+                "jaccard2": lambda z: R_pl.jaccard_loss(t_int, z),
+                "tversky2": lambda z: R_pl.tversky_loss(t_int, z, 0.3, 0.7),
+            })
+        pre = f"c{i}_"
+        out.update({pre + "logits": z0, pre + "target": tgt.astype(np.uint8) if is_int else tgt})
+        line = []
+        for name, fn in cases.items():
+            z = torch.tensor(z0, requires_grad=True)
+            v = fn(z)
+            v.backward()
+            out[pre + name] = np.float64(float(v.detach()))
+            if not name.startswith("bce_") or name == "bce_pw":
+                if keep_grads[kind] is None or name in keep_grads[kind]:
+                    out[pre + "d" + name] = z.grad.numpy().copy()
+            line.append(f"{name} {float(v.detach()):.6f}")
+        with torch.no_grad():
+            z = torch.tensor(z0)
+            if kind == "int":
+                out[pre + "logits_b"] = zb
+                out[pre + "mse_map"] = R_l1.softmax_mse_loss(z, torch.tensor(zb), sigmoid=True).numpy().copy()
+            for thr, tag in ((None, "none"), (0.5, "t05")):
+                out[pre + "iou_" + tag] = np.float64(float(R_l2.iou(z, t_f, threshold=thr)))
+                out[pre + "fscore_" + tag] = np.float64(float(R_l2.f_score(z, t_f, threshold=thr)))
+                out[pre + "fscore_b2_" + tag] = np.float64(float(R_l2.f_score(z, t_f, beta=2, threshold=thr)))
+        print(f"g12 case {i} {kind}: " + " ".join(line))
+    R_l2.F = F
+    path = os.path.join(OUT, "g12_binary.npz")
+    np.savez_compressed(path, **out)
+    print(f"g12: {os.path.getsize(path)} bytes")
+
+
 def main():
     torch.set_num_threads(4)
     only = sys.argv[1:]                      # e.g. `python tools/make_golden.py g9`: that fixture alone
@@ -716,6 +811,7 @@ def main():
     g9()
     g10()
     make_g11_seglosses()
+    make_g12_binary()
 
 
 if __name__ == "__main__":

@@ -18,6 +18,10 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   UCCTrainer, ucc_loss, ucc_scalars, cutmix_batch, cutmix_rects   (UCC/UCC_train.py, UCC/cross_cutmix.py; net_factory("unet_ucc"))
   SegLoss, seg_scalars, jaccard_loss, tversky_loss, FocalLoss, DiceLoss, seg_losses.ce_loss   the supervised loss family
                                                     (utilities/pytorch_losses.py, losses_1.py); BaselineTrainer(loss=SegLoss(...))
+  BinarySegLoss, bin_scalars, bin_confusion, bin_metrics_from_confusion, sigmoid_mse_loss, sigmoid_kl_loss, BinaryTrainer
+                                                    one-channel sigmoid heads; the reference-named binary losses (bce_loss, FocalLoss,
+                                                    JaccardLoss, BCEDiceLoss, iou, f_score, ...: utilities/losses_2.py) live in
+                                                    `uaps_amd.binary_losses`, beside the softmax names above
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -34,6 +38,9 @@ from .cct_dct import CCTTrainer, DCTTrainer, cct_consistency, rot_consistency, r
 from .cps import CPSTrainer, cps_loss, cps_scalars
 from .ucc import UCCTrainer, ucc_loss, ucc_scalars, cutmix_batch, cutmix_rects
 from .seg_losses import SegLoss, seg_scalars, jaccard_loss, tversky_loss, FocalLoss, DiceLoss
+from .binary_losses import BinarySegLoss, bin_scalars, bin_confusion, bin_metrics_from_confusion, sigmoid_mse_loss, sigmoid_kl_loss
+from .binary_trainer import BinaryTrainer
+from . import binary_losses, binary_trainer
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -147,6 +147,14 @@ SIGNATURES = {
     "uaps_segloss_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
     "uaps_segloss_fwd": (C.c_int, [_PTR] * 3 + [C.c_int] * 4 + [_PTR, _PTR, C.c_size_t, _PTR]),
     "uaps_segloss_bwd": (C.c_int, [_PTR] * 5 + [C.c_int] * 4 + [_PTR, _PTR]),
+    "uaps_binloss_workspace_bytes": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_size_t)]),
+    "uaps_binloss_fwd": (C.c_int, [_PTR] * 3 + [C.c_int] * 3 + [_PTR, _PTR, C.c_size_t, _PTR]),
+    "uaps_binloss_bwd": (C.c_int, [_PTR] * 5 + [C.c_int] * 3 + [_PTR, _PTR]),
+    "uaps_sigmoid_mse_fwd": (C.c_int, [_PTR, _PTR, C.c_long, _PTR, _PTR]),
+    "uaps_sigmoid_mse_bwd": (C.c_int, [_PTR, _PTR, _PTR, C.c_long, _PTR, _PTR]),
+    "uaps_sigmoid_kl_fwd": (C.c_int, [_PTR, _PTR, C.c_long, _PTR, _PTR, C.c_size_t, _PTR]),
+    "uaps_sigmoid_kl_bwd": (C.c_int, [_PTR, _PTR, _PTR, C.c_long, _PTR, _PTR]),
+    "uaps_bin_confusion": (C.c_int, [_PTR, _PTR] + [C.c_int] * 3 + [C.c_double, _PTR, _PTR]),
 }
 
 
@@ -283,6 +291,17 @@ class SegLossParams(C.Structure):
                 ("class_weight", C.c_float * SEG_MAX_CLASSES), ("focal_alpha", C.c_float * SEG_MAX_CLASSES), ("focal_gamma", C.c_float),
                 ("focal_mean", C.c_int), ("dice_sq_weight", C.c_float * SEG_MAX_CLASSES), ("tversky_alpha", C.c_float),
                 ("tversky_beta", C.c_float), ("eps", C.c_float), ("smooth", C.c_float), ("ignore_index", C.c_int64)]
+
+
+BIN_NTERMS, BIN_NSCALARS = 7, 24       # UAPS_BIN_NTERMS, UAPS_BIN_S_NSCALARS
+
+
+class BinLossParams(C.Structure):
+    """uaps_binloss_params (include/uaps_hip.h): passed by value into the kernels of uaps_binloss_fwd / _bwd."""
+    _fields_ = [("struct_size", C.c_uint32), ("terms", C.c_uint32), ("coef", C.c_float * BIN_NTERMS), ("target_float", C.c_uint32),
+                ("has_pos_weight", C.c_uint32), ("pos_weight", C.c_float), ("focal_alpha", C.c_float), ("focal_gamma", C.c_float),
+                ("focal_mean", C.c_int), ("beta", C.c_float), ("tversky_alpha", C.c_float), ("tversky_beta", C.c_float),
+                ("eps", C.c_float)]
 
 
 def mk_hints(bounds=(), out_amax=None, stats=None, residual=None, dyt=None, bsum=None):

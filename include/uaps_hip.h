@@ -989,6 +989,80 @@ int uaps_augment_batch(const uint8_t* images_hwc, const uint8_t* masks, const in
                        const float* std3_host, float* out, int64_t* out_mask, uaps_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Input pipeline, any recipe, one or two views per source (csrc/augment_views.hip): the dataset variants of the reference's
+ * loaders (DAGM / KoSDD2 / MTiles UAPS_dataloaders.py, UCC/UCC_dataloaders.py:149-168) differ in the ORDER of their stages, in the
+ * channel count and in the stages they use, so the gather kernel runs a small program per (view, image).  PARITY UNPINNED, as
+ * above: the arithmetic is the one written down here, not a measured equality with cv2 / albumentations.
+ *
+ * Geometry comes first, as one coordinate map: frame = rot90^rot_k(vflip(hflip(resize_nearest(source)))), the "working frame"
+ * [Ho][Wo] (rot_k odd needs Ho == Wo).  The program then runs in that frame, on uint8 grey levels held as float; every op ends
+ * in a clip to 0..255.  uaps_view_row::op[i] with its operands a[i], b[i]; UAPS_AUG_END (0) ends the program:
+ *   UAPS_AUG_BC        trunc(clip(v * a + b * 255))                                    (uaps_augment_batch's line)
+ *   UAPS_AUG_NOISE     trunc(clip(v + g)); g = noise[view][image][channel][y][x] (already scaled by sigma) or, without a field,
+ *                      a * N(0,1) from Philox + Box-Muller keyed by (seed, op index, view, image, pixel)
+ *   UAPS_AUG_BLUR      a = k in {3, 5, 7}: rint(mean of the k x k window), BORDER_REFLECT_101, half to even
+ *   UAPS_AUG_BRIGHT    trunc(clip(v * a))
+ *   UAPS_AUG_CONTRAST  trunc(clip(v * a + m * (1 - a))), m = rint(mean over the frame of grey) of the image as it enters the
+ *                      op, grey = (299 R + 587 G + 114 B) / 1000 (the channel itself when Cs == 1); computed by a pre-pass in
+ *                      integers, fixed-order two-stage reduction, so m is exact and deterministic
+ *   UAPS_AUG_SATURATE  rint(clip(grey + a * (v - grey))), grey = 0.299 R + 0.587 G + 0.114 B in float; identity when Cs == 1
+ *   UAPS_AUG_HUE       hexcone RGB -> HSV in float, H <- frac(H + a), back, rint, clip; identity when Cs == 1
+ *   UAPS_AUG_PIXDROP   u = drop_u[view][image][y][x] or one Philox uniform per pixel; all channels 0 where u < a; mask untouched
+ *   UAPS_AUG_GRID      the frame is resampled: pixel (y, x) becomes the bilinear sample (float weights, reflect-101 indices,
+ *                      rint) at (grid_ys[view][image][y], grid_xs[view][image][x]), positions clamped to the frame; the mask
+ *                      takes the node nearest to that position (rint).  uaps_view_row::grid_on must be set exactly when the
+ *                      program holds this op.
+ * GRID and BLUR split a program into three segments: ops before GRID are evaluated at the four bilinear corners, ops between
+ * GRID and BLUR at every blur tap, ops after BLUR once.  Forms that do not exist (UAPS_ENOFORM, nothing launched): NOISE or
+ * PIXDROP ahead of GRID, BLUR ahead of GRID, more than one GRID / BLUR, and more than one CONTRAST (the second one's mean would
+ * need the first one's pre-pass to have finished inside its own).
+ *
+ * Every operand travels in one size-versioned struct (fields are only ever appended; struct_size = sizeof of the caller's header).
+ * rows_host and rows are the SAME [V][B] rows on the host (read here, for validation and planning only) and on the device (read
+ * by the kernels).  workspace: uaps_augment_views_workspace_bytes, needed only when a program holds CONTRAST (NULL / 0 otherwise);
+ * on return of the stream's work its first V * B floats hold m per (view, image), -1 where the program has no CONTRAST.
+ * The call does not synchronise.  Errors (nothing launched): UAPS_EINVAL null pointer, dimension, V outside {1, 2}, Cs outside
+ * {1, 3}, unknown op, blur size, rot_k, grid_on without maps; UAPS_ERANGE V * B > 65535 or a frame beyond 2^31 - 1 pixels; UAPS_EWORKSPACE.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_AUG_END 0
+#define UAPS_AUG_BC 1
+#define UAPS_AUG_NOISE 2
+#define UAPS_AUG_BLUR 3
+#define UAPS_AUG_BRIGHT 4
+#define UAPS_AUG_CONTRAST 5
+#define UAPS_AUG_SATURATE 6
+#define UAPS_AUG_HUE 7
+#define UAPS_AUG_PIXDROP 8
+#define UAPS_AUG_GRID 9
+#define UAPS_AUG_MAX_OPS 8
+typedef struct uaps_view_row {
+    int32_t hflip, vflip, rot_k, grid_on;        /* the geometry row */
+    int32_t op[UAPS_AUG_MAX_OPS];                /* the program, executed in order */
+    float a[UAPS_AUG_MAX_OPS], b[UAPS_AUG_MAX_OPS];
+} uaps_view_row;
+typedef struct uaps_augment_views_call {
+    uint32_t struct_size;
+    int32_t V, B, Hs, Ws, Cs, Ho, Wo;
+    const uint8_t* images;                       /* [B][Hs][Ws][Cs] */
+    const uint8_t* masks;                        /* [B][Hs][Ws] or NULL */
+    const uaps_view_row* rows_host;              /* [V][B], host */
+    const uaps_view_row* rows;                   /* [V][B], device, same contents */
+    const float* grid_ys;                        /* [V][B][Ho] device, or NULL when no row has grid_on */
+    const float* grid_xs;                        /* [V][B][Wo] */
+    const float* noise;                          /* [V][B][Cs][Ho][Wo] device or NULL */
+    const float* drop_u;                         /* [V][B][Ho][Wo] device or NULL */
+    uint64_t seed;
+    float mean[3], std[3];                       /* the first Cs are used */
+    float* out;                                  /* [V][B][Cs][Ho][Wo] */
+    int64_t* out_mask;                           /* [V][B][Ho][Wo], NULL exactly when masks is */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_augment_views_call;
+int uaps_augment_views_workspace_bytes(int V, int B, int Ho, int Wo, size_t* bytes);
+int uaps_augment_views(const uaps_augment_views_call* call);
+
+/* ---------------------------------------------------------------------------------------------
  * Optimizer: torch.optim.Adam(model.parameters(), lr) of UAPS_train.py:112, stepped at :292 -- one multi-tensor
  * launch per 48 tensors instead of PyTorch's per-chunk foreach kernels.  Host arrays of n device pointers / sizes;
  * `step` is the 1-based step count (bias corrections 1 - beta^step are computed on the host in double).

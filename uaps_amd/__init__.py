@@ -41,6 +41,8 @@ from .seg_losses import SegLoss, seg_scalars, jaccard_loss, tversky_loss, FocalL
 from .binary_losses import BinarySegLoss, bin_scalars, bin_confusion, bin_metrics_from_confusion, sigmoid_mse_loss, sigmoid_kl_loss
 from .binary_trainer import BinaryTrainer
 from . import binary_losses, binary_trainer
+from .pipelines import Recipe, Stage, RECIPES, ViewDraws, draw, augment_views, ArrayBatches, UCCArrayBatches
+from . import pipelines
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

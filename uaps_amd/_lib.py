@@ -109,6 +109,8 @@ SIGNATURES = {
     "uaps_feat_dropout_stats": (C.c_int, [_PTR] + [C.c_int] * 4 + [_PTR, C.c_size_t, _PTR]),
     "uaps_fanout_perturbed": (C.c_int, [_PTR] * 7 + [C.c_int, C.c_int, C.c_uint64, C.c_float, C.c_float] + [C.c_int] * 4 + [_PTR]),
     "uaps_augment_batch": (C.c_int, [_PTR] * 5 + [C.c_uint64] + [C.c_int] * 5 + [C.POINTER(C.c_float), C.POINTER(C.c_float), _PTR, _PTR, _PTR]),
+    "uaps_augment_views_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
+    "uaps_augment_views": (C.c_int, [_PTR]),
     "uaps_softmax_klmap_bwd": (C.c_int, [_PTR] * 3 + [C.c_int] * 4 + [_PTR] * 3),
     "uaps_softmax_pair_fwd": (C.c_int, [_PTR, _PTR] + [C.c_int] * 5 + [_PTR, _PTR, _PTR, _PTR, C.c_size_t, _PTR]),
     "uaps_softmax_mse_bwd": (C.c_int, [_PTR] * 3 + [C.c_int] * 4 + [_PTR, _PTR]),
@@ -275,6 +277,25 @@ class ConvCall(C.Structure):
                 ("w_packed", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("y2", C.c_void_p), ("y_grad", C.c_void_p),
                 ("stats", C.c_void_p), ("xf", C.c_void_p), ("xf_slope", C.c_float), ("xf_groups", C.c_int), ("want_bias", C.c_int),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p), ("hints", CallHints)]
+
+
+AUG_MAX_OPS = 8                         # UAPS_AUG_MAX_OPS
+AUG_END, AUG_BC, AUG_NOISE, AUG_BLUR, AUG_BRIGHT, AUG_CONTRAST, AUG_SATURATE, AUG_HUE, AUG_PIXDROP, AUG_GRID = range(10)   # UAPS_AUG_*
+
+
+class ViewRow(C.Structure):
+    """uaps_view_row (include/uaps_hip.h): the geometry row and the program of one (view, image)."""
+    _fields_ = [("hflip", C.c_int32), ("vflip", C.c_int32), ("rot_k", C.c_int32), ("grid_on", C.c_int32),
+                ("op", C.c_int32 * AUG_MAX_OPS), ("a", C.c_float * AUG_MAX_OPS), ("b", C.c_float * AUG_MAX_OPS)]
+
+
+class AugmentViewsCall(C.Structure):
+    """uaps_augment_views_call (include/uaps_hip.h): every operand of uaps_augment_views, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("V", C.c_int32), ("B", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("Cs", C.c_int32),
+                ("Ho", C.c_int32), ("Wo", C.c_int32), ("images", C.c_void_p), ("masks", C.c_void_p), ("rows_host", C.c_void_p),
+                ("rows", C.c_void_p), ("grid_ys", C.c_void_p), ("grid_xs", C.c_void_p), ("noise", C.c_void_p), ("drop_u", C.c_void_p),
+                ("seed", C.c_uint64), ("mean", C.c_float * 3), ("std", C.c_float * 3), ("out", C.c_void_p), ("out_mask", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
 SEG_NTERMS, SEG_MAX_CLASSES = 6, 8      # UAPS_SEG_NTERMS, UAPS_MAX_CLASSES

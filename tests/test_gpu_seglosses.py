@@ -49,6 +49,14 @@ def test_seg_losses_match_the_reference_fixture(through):
 _SHAPES = [(3, 37, 53), (2, 1, 40), (4, 32, 40), (2, 16, 24)]
 _SWEEP = [(B, C, H, W, ign, False) for C in (2, 3, 4, 7, 8) for B, H, W in _SHAPES for ign in (False, True)]
 _SWEEP += [(2, 4, 16, 24, True, True), (2, 7, 16, 24, False, True)]      # logits one float off 16-byte alignment: one pixel a lane
+# more items than the 1024 x 256 lanes of the largest grid, so lanes take a second trip through the grid-stride loop: 262 205
+# one-pixel items (229 x 229 is odd) and 278 528 four-pixel items.  These two run the all-six-terms spec only.
+_MULTI_TRIP = [(5, 2, 229, 229, True, False), (17, 2, 256, 256, True, False)]
+_SWEEP += _MULTI_TRIP
+# Bars: 1e-5 on the terms, the gradient and the class sum of a pixel's gradient (of max|g|).  A case that does not hold them gets
+# 4 x the error of the same restatement evaluated in fp32 by torch on the CPU against the float64 one, measured on that case
+# (profiles/segloss_forms_tau.txt): (B, C, H, W) -> {quantity: bar}.
+_TAU = {}
 
 
 def _specs(C, gen):
@@ -83,8 +91,8 @@ def _device_logits(z, misaligned):
 @pytest.mark.parametrize("B,C,H,W,ign,misaligned", _SWEEP)
 def test_seg_kernels_vs_float64(B, C, H, W, ign, misaligned):
     """The bars of test_cps_kernels_vs_float64 (the same arithmetic: fp32 exp / log / division a few ulp per pixel, fp32 sums over at
-    most a block's pixels and double across blocks): terms rtol 1e-5, gradient error <= 1e-5 max|g|, class sum of each pixel's
-    gradient <= 1e-5 max|g|; two runs give the same bits."""
+    most a lane's pixels, then a block's lanes, and double across blocks): terms rtol 1e-5, gradient error <= 1e-5 max|g|, class sum
+    of each pixel's gradient <= 1e-5 max|g| (see _TAU); two runs give the same bits."""
     from uaps_amd import seg_losses as S
     gen = torch.Generator().manual_seed(B * 131 + C * 17 + H * 3 + W + 7 * ign)
     z = torch.randn(B, C, H, W, generator=gen) * 2
@@ -94,7 +102,9 @@ def test_seg_kernels_vs_float64(B, C, H, W, ign, misaligned):
         ignore = 255
         y[:, :, 3:9] = 255                                   # a planted strip
         y[0, 0, 0] = 255
-    for coefs, kw in _specs(C, gen):
+    tau = {"terms": 1e-5, "grad": 1e-5, "sum": 1e-5, **_TAU.get((B, C, H, W), {})}
+    specs = _specs(C, gen)
+    for coefs, kw in specs[:1] if (B, C, H, W, ign, misaligned) in _MULTI_TRIP else specs:
         zd = z.double().requires_grad_(True)
         ref, terms = _ref_loss(coefs, kw, y, zd, ignore)
         ref.backward()
@@ -106,15 +116,15 @@ def test_seg_kernels_vs_float64(B, C, H, W, ign, misaligned):
         tag = (tuple(coefs), kw["focal_gamma"])
         for k in coefs:
             print(tag, k, float(sc[k]), float(terms[k]))
-            np.testing.assert_allclose(float(sc[k]), float(terms[k]), rtol=1e-5, err_msg=str((tag, k)))
-        np.testing.assert_allclose(float(out.loss.detach()), float(ref.detach()), rtol=1e-5, err_msg=str(tag))
+            np.testing.assert_allclose(float(sc[k]), float(terms[k]), rtol=tau["terms"], err_msg=str((tag, k)))
+        np.testing.assert_allclose(float(out.loss.detach()), float(ref.detach()), rtol=tau["terms"], err_msg=str(tag))
         assert float(sc["bad"]) == 0.0 and float(sc["n_valid"]) == float((y != 255).sum())
         scale = float(zd.grad.abs().max())
         err = float((zg.grad.cpu().double() - zd.grad).abs().max())
         csum = float(zg.grad.sum(dim=1).abs().max())
         print(tag, "grad err", err, "class sum", csum, "scale", scale)
-        assert err <= 1e-5 * scale, (tag, err, scale)
-        assert csum <= 1e-5 * scale, (tag, csum, scale)
+        assert err <= tau["grad"] * scale, (tag, err, scale)
+        assert csum <= tau["sum"] * scale, (tag, csum, scale)
         if ign:
             assert float(zg.grad[:, :, :, 3:9].abs().max()) == 0.0           # ignored pixels: exactly zero
         # two runs give the same bits

@@ -18,14 +18,13 @@
 #include <string.h>
 #include <math.h>
 #include "../../include/uaps_hip.h"
-#include "hints.hpp"
+#include "loss_common.hpp"
 
 namespace {
-constexpr int kThreads = 256;
+using namespace uaps::loss;
 constexpr int kMaxBlocks = 512;
 constexpr int kSums = 7;                       // columns of a partial row: see Acc
 constexpr int kCols = 8;                       // floats of a block's partial row
-constexpr double kTooBig = 2147483648.0;       // bytes: every tensor an entry point takes stays below 2 GiB
 
 struct Acc { float bce = 0.f, focal = 0.f, n = 0.f, P = 0.f, G = 0.f, I = 0.f, bad = 0.f; };
 
@@ -142,11 +141,7 @@ __global__ __launch_bounds__(64) void bin_finalize(const float* __restrict__ par
                                                    float* __restrict__ s) {
     __shared__ double sum[kCols];
     const int t = threadIdx.x;
-    if (t < kSums) {
-        double acc = 0.0;
-        for (int i = 0; i < blocks; ++i) acc += (double)partials[(long)i * kCols + t];
-        sum[t] = acc;
-    }
+    column_sums<kCols>(partials, 0, blocks, kSums, sum);
     __syncthreads();
     if (t != 0) return;
     const double n = sum[2], P = sum[3], G = sum[4], I = sum[5];
@@ -304,7 +299,7 @@ __device__ __forceinline__ float sig_kl_element(float x, float y) {
 
 __global__ __launch_bounds__(kThreads) void sig_kl_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b, long nvec, long N,
                                                               float* __restrict__ partials) {
-    __shared__ float red[kThreads / 64];
+    __shared__ float red[kWaves];
     const long stride = (long)gridDim.x * kThreads, first = (long)blockIdx.x * kThreads + threadIdx.x;
     float acc = 0.f;
     for (long i = first; i < nvec; i += stride) {
@@ -312,11 +307,8 @@ __global__ __launch_bounds__(kThreads) void sig_kl_fwd_kernel(const float* __res
         acc += (sig_kl_element(x.x, y.x) + sig_kl_element(x.y, y.y)) + (sig_kl_element(x.z, y.z) + sig_kl_element(x.w, y.w));
     }
     for (long i = 4 * nvec + first; i < N; i += stride) acc += sig_kl_element(a[i], b[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);       // ONE sum: six shuffle steps are the cheap form here
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    const float s = block_sum(acc, red);                                  // ONE sum: six shuffle steps are the cheap form here
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(64) void sig_kl_finalize(const float* __restrict__ partials, int blocks, double inv_n, float* __restrict__ out) {
@@ -368,10 +360,8 @@ __global__ __launch_bounds__(kThreads) void bin_confusion_kernel(const float* __
 
 __global__ void zero4_kernel(unsigned long long* counts) { if (threadIdx.x < 4) counts[threadIdx.x] = 0ull; }
 
-inline int grid_for(long items) { long g = (items + kThreads - 1) / kThreads; return (int)(g > kMaxBlocks ? kMaxBlocks : (g < 1 ? 1 : g)); }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// the launch's work items: the four-element groups where they exist, else the elements
-inline long items_of(long nvec, long N) { return nvec > 0 ? nvec : N; }
+// the launch's grid: over the four-element groups where they exist, else over the elements
+inline int grid_of(long nvec, long N) { return grid_for(nvec > 0 ? nvec : N, kMaxBlocks); }
 
 int check_shape(int B, int H, int W, bool labels64) {
     if (B <= 0 || H <= 0 || W <= 0) return UAPS_EINVAL;
@@ -415,7 +405,7 @@ extern "C" int uaps_binloss_fwd(const float* z, const void* target, const uaps_b
     if (rc) return rc;
     if (!workspace || workspace_bytes < kWorkspaceBytes) return UAPS_EWORKSPACE;
     const long N = (long)B * H * W, nvec = (al16(z) && al16(target)) ? N / 4 : 0;
-    const int grid = grid_for(items_of(nvec, N));
+    const int grid = grid_of(nvec, N);
     hipStream_t st = (hipStream_t)stream;
     uaps::account_bytes((p.target_float ? 8.0 : 12.0) * (double)N);
     if (p.target_float)
@@ -436,7 +426,7 @@ extern "C" int uaps_binloss_bwd(const float* z, const void* target, const uaps_b
     if (!rc) rc = check_shape(B, H, W, !p.target_float);
     if (rc) return rc;
     const long N = (long)B * H * W, nvec = (al16(z) && al16(target) && al16(dz)) ? N / 4 : 0;
-    const int grid = grid_for(items_of(nvec, N));
+    const int grid = grid_of(nvec, N);
     hipStream_t st = (hipStream_t)stream;
     uaps::account_bytes((p.target_float ? 12.0 : 16.0) * (double)N);
     if (p.target_float)
@@ -452,7 +442,7 @@ extern "C" int uaps_sigmoid_mse_fwd(const float* a, const float* b, long n, floa
     if (rc) return rc;
     const long nvec = (al16(a) && al16(b) && al16(out)) ? n / 4 : 0;
     uaps::account_bytes(12.0 * (double)n);
-    UAPS_LAUNCH_MAIN(sig_mse_fwd_kernel, dim3(grid_for(items_of(nvec, n))), dim3(kThreads), 0, (hipStream_t)stream, a, b, nvec, n, out);
+    UAPS_LAUNCH_MAIN(sig_mse_fwd_kernel, dim3(grid_of(nvec, n)), dim3(kThreads), 0, (hipStream_t)stream, a, b, nvec, n, out);
     return (int)hipGetLastError();
 }
 
@@ -462,7 +452,7 @@ extern "C" int uaps_sigmoid_mse_bwd(const float* a, const float* b, const float*
     if (rc) return rc;
     const long nvec = (al16(a) && al16(b) && al16(g_map) && al16(da)) ? n / 4 : 0;
     uaps::account_bytes(16.0 * (double)n);
-    UAPS_LAUNCH_MAIN(sig_mse_bwd_kernel, dim3(grid_for(items_of(nvec, n))), dim3(kThreads), 0, (hipStream_t)stream, a, b, g_map, nvec, n, da);
+    UAPS_LAUNCH_MAIN(sig_mse_bwd_kernel, dim3(grid_of(nvec, n)), dim3(kThreads), 0, (hipStream_t)stream, a, b, g_map, nvec, n, da);
     return (int)hipGetLastError();
 }
 
@@ -473,7 +463,7 @@ extern "C" int uaps_sigmoid_kl_fwd(const float* a, const float* b, long n, float
     if (rc) return rc;
     if (!workspace || workspace_bytes < kWorkspaceBytes) return UAPS_EWORKSPACE;
     const long nvec = (al16(a) && al16(b)) ? n / 4 : 0;
-    const int grid = grid_for(items_of(nvec, n));
+    const int grid = grid_of(nvec, n);
     hipStream_t st = (hipStream_t)stream;
     uaps::account_bytes(8.0 * (double)n);
     UAPS_LAUNCH_MAIN(sig_kl_fwd_kernel, dim3(grid), dim3(kThreads), 0, st, a, b, nvec, n, (float*)workspace);
@@ -489,7 +479,7 @@ extern "C" int uaps_sigmoid_kl_bwd(const float* a, const float* b, const float* 
     if (rc) return rc;
     const long nvec = (al16(a) && al16(b) && al16(da)) ? n / 4 : 0;
     uaps::account_bytes(12.0 * (double)n);
-    UAPS_LAUNCH_MAIN(sig_kl_bwd_kernel, dim3(grid_for(items_of(nvec, n))), dim3(kThreads), 0, (hipStream_t)stream, a, b, grad,
+    UAPS_LAUNCH_MAIN(sig_kl_bwd_kernel, dim3(grid_of(nvec, n)), dim3(kThreads), 0, (hipStream_t)stream, a, b, grad,
                      (float)(1.0 / (double)n), nvec, n, da);
     return (int)hipGetLastError();
 }
@@ -507,7 +497,7 @@ extern "C" int uaps_bin_confusion(const float* z, const int64_t* labels, int B, 
     hipLaunchKernelGGL(zero4_kernel, dim3(1), dim3(64), 0, st, (unsigned long long*)counts);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    UAPS_LAUNCH_MAIN(bin_confusion_kernel, dim3(grid_for(N)), dim3(kThreads), 0, st, z, (const long long*)labels, cut, N,
+    UAPS_LAUNCH_MAIN(bin_confusion_kernel, dim3(grid_for(N, kMaxBlocks)), dim3(kThreads), 0, st, z, (const long long*)labels, cut, N,
                      (unsigned long long*)counts);
     return (int)hipGetLastError();
 }

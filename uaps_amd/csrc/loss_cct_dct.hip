@@ -13,61 +13,24 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/uaps_hip.h"
-#include "hints.hpp"
+#include "loss_common.hpp"
 
 namespace {
-constexpr int kThreads = 256;
+using namespace uaps::loss;
+using namespace uaps::pixel;
 constexpr int kMaxBlocks = 1024;
 constexpr int kTile = 32;                      // output tile edge of the rotation kernels; 256 threads = 32 columns x 8 rows
 constexpr int kTerms = UAPS_CCT_MAX_HEADS;     // partial sums per block (D - 1 used)
-constexpr double kTooBig = 2147483648.0;       // bytes: every tensor an entry point takes stays below 2 GiB
 
 struct Heads { const float* z[UAPS_CCT_MAX_HEADS]; };
 struct GradHeads { float* z[UAPS_CCT_MAX_HEADS]; };
 
-// p[c][v] = softmax over c of the logits z[c * HW + v]
+// p[c][v] = softmax over c of the logits z[c * HW + v] (the max and the log-sum-exp of softmax_inplace are not used: dead code here)
 template <int C, int V>
 __device__ __forceinline__ void load_softmax(const float* __restrict__ z, long HW, float (&p)[C][V]) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        if constexpr (V == 4) {
-            const float4 t = *reinterpret_cast<const float4*>(z + (long)c * HW);
-            p[c][0] = t.x; p[c][1] = t.y; p[c][2] = t.z; p[c][3] = t.w;
-        } else {
-            p[c][0] = z[(long)c * HW];
-        }
-    }
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-        float mx = p[0][v];
-#pragma unroll
-        for (int c = 1; c < C; ++c) mx = fmaxf(mx, p[c][v]);
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) { p[c][v] = expf(p[c][v] - mx); s += p[c][v]; }
-#pragma unroll
-        for (int c = 0; c < C; ++c) p[c][v] = p[c][v] / s;
-    }
-}
-
-template <int C, int V>
-__device__ __forceinline__ void store_planes(float* __restrict__ dz, long HW, const float (&g)[C][V]) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        if constexpr (V == 4)
-            *reinterpret_cast<float4*>(dz + (long)c * HW) = make_float4(g[c][0], g[c][1], g[c][2], g[c][3]);
-        else
-            dz[(long)c * HW] = g[c][0];
-    }
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();                                  // red is reused by the next sum of the block
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
+    float mx[V], lse[V];
+    load_logits<C, V>(z, HW, p);
+    softmax_inplace<C, V>(p, mx, lse);
 }
 
 // ---- CCT ----------------------------------------------------------------------------------------------------------------------
@@ -75,7 +38,7 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 // pixels of sum_c (p0 - pk)^2.
 template <int C, int V>
 __global__ __launch_bounds__(kThreads) void cct_fwd_kernel(Heads h, int D, long HW, long off0, long groups, float* __restrict__ partials) {
-    __shared__ float red[kThreads / 64];
+    __shared__ float red[kWaves];
     float acc[kTerms - 1];
 #pragma unroll
     for (int k = 0; k < kTerms - 1; ++k) acc[k] = 0.f;
@@ -253,7 +216,7 @@ __global__ __launch_bounds__(kThreads) void rot_cons_kernel(const float* __restr
                                                             int B, int H, int W, int k, int tiles_i, int tiles_j, const float* __restrict__ grad,
                                                             float coef, float* __restrict__ dr, float* __restrict__ du, float* __restrict__ partials) {
     __shared__ float tile[C][kTile][kTile + 1];
-    __shared__ float red[kThreads / 64];
+    __shared__ float red[kWaves];
     const int Ho = (k & 1) ? W : H, Wo = (k & 1) ? H : W;
     const long HW = (long)H * W;
     const int per_img = tiles_i * tiles_j;
@@ -333,24 +296,17 @@ __global__ __launch_bounds__(kThreads) void rot_cons_kernel(const float* __restr
     }
 }
 
-inline int grid_for(long n) { long g = (n + kThreads - 1) / kThreads; return (int)(g > kMaxBlocks ? kMaxBlocks : (g < 1 ? 1 : g)); }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // (each returns the grid it launched: the forward's finalize reads one partial row per block)
 template <int C> int run_cct_fwd(bool vec, const Heads& h, int D, long HW, long off0, long npix, float* partials, hipStream_t st) {
-    if (vec) {
-        UAPS_LAUNCH_MAIN((cct_fwd_kernel<C, 4>), dim3(grid_for(npix / 4)), dim3(kThreads), 0, st, h, D, HW, off0, npix / 4, partials);
-        return grid_for(npix / 4);
-    }
-    UAPS_LAUNCH_MAIN((cct_fwd_kernel<C, 1>), dim3(grid_for(npix)), dim3(kThreads), 0, st, h, D, HW, off0, npix, partials);
-    return grid_for(npix);
+    const long groups = npix / (vec ? 4 : 1);
+    const int grid = grid_for(groups, kMaxBlocks);
+    UAPS_LAUNCH_V(vec, cct_fwd_kernel, C, grid, st, h, D, HW, off0, groups, partials);
+    return grid;
 }
 template <int C> int run_cct_bwd(bool vec, const Heads& h, const GradHeads& dh, int D, const float* g, float coef, long HW, long off0, long npix,
                                  hipStream_t st) {
-    if (vec)
-        UAPS_LAUNCH_MAIN((cct_bwd_kernel<C, 4>), dim3(grid_for(npix / 4)), dim3(kThreads), 0, st, h, dh, D, g, coef, HW, off0, npix / 4);
-    else
-        UAPS_LAUNCH_MAIN((cct_bwd_kernel<C, 1>), dim3(grid_for(npix)), dim3(kThreads), 0, st, h, dh, D, g, coef, HW, off0, npix);
+    const long groups = npix / (vec ? 4 : 1);
+    UAPS_LAUNCH_V(vec, cct_bwd_kernel, C, grid_for(groups, kMaxBlocks), st, h, dh, D, g, coef, HW, off0, groups);
     return 0;
 }
 template <int C, bool BWD> int run_rot(int grid, const float* r, const float* u, long r_off, long u_off, int B, int H, int W, int k, int ti, int tj,
@@ -358,9 +314,6 @@ template <int C, bool BWD> int run_rot(int grid, const float* r, const float* u,
     UAPS_LAUNCH_MAIN((rot_cons_kernel<C, BWD>), dim3(grid), dim3(kThreads), 0, st, r, u, r_off, u_off, B, H, W, k, ti, tj, g, coef, dr, du, partials);
     return 0;
 }
-#define UAPS_BY_C(C, CALL) \
-    switch (C) { case 2: return CALL(2); case 3: return CALL(3); case 4: return CALL(4); case 5: return CALL(5); \
-                 case 6: return CALL(6); case 7: return CALL(7); case 8: return CALL(8); default: return 0; }
 
 int cct_fwd_dispatch(int C, bool vec, const Heads& h, int D, long HW, long off0, long npix, float* partials, hipStream_t st) {
 #define CALL(K) run_cct_fwd<K>(vec, h, D, HW, off0, npix, partials, st)
@@ -469,7 +422,7 @@ static int rot90_batch_impl(float* amax, const float* x_l, const float* x_u, int
     float* rot = rot_out ? rot_out : out + 2 * n;
     uaps::account_bytes(4.0 * 6.0 * n);                   // x_l, x_u read (x_u twice), 3 n written
     const long n4 = (al16(x_l) && al16(x_u) && al16(out) && n % 4 == 0) ? n / 4 : 0;
-    const int cat_blocks = grid_for(n4 > 0 ? 2 * n4 : n);
+    const int cat_blocks = grid_for(n4 > 0 ? 2 * n4 : n, kMaxBlocks);
     int ti, tj;
     const double blocks = (double)cat_blocks + (double)B * Cin * tiles_of(H, W, k, ti, tj);
     if (blocks >= 2147483647.0) return UAPS_ERANGE;

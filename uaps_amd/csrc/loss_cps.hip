@@ -16,16 +16,13 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/uaps_hip.h"
-#include "hints.hpp"
-#include "loss_pixel.hpp"
+#include "loss_common.hpp"
 
 namespace {
+using namespace uaps::loss;
 using namespace uaps::pixel;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
 constexpr int kMaxBlocks = 512;                // per row set (labelled / unlabelled)
 constexpr int kCols = 80;                      // floats of a block's partial row: 5 + 9 C used (77 at C = 8)
-constexpr double kTooBig = 2147483648.0;       // bytes: every tensor an entry point takes stays below 2 GiB
 
 // columns of a partial row (m = 0, 1: the network)
 //   [0, 2)       CE sum of network m against the ground truth           (labelled blocks)
@@ -99,14 +96,8 @@ __global__ __launch_bounds__(kThreads) void cps_fwd_kernel(const float* __restri
         bad += load_labels<C, V>(labels, n, lab, y);
         argmax_logits<C, V>(a, am1);
         argmax_logits<C, V>(b, am2);
-        if (pseudo1 != nullptr) {
-            if constexpr (V == 4) *reinterpret_cast<uchar4*>(pseudo1 + n) = make_uchar4((uint8_t)am1[0], (uint8_t)am1[1], (uint8_t)am1[2], (uint8_t)am1[3]);
-            else pseudo1[n] = (uint8_t)am1[0];
-        }
-        if (pseudo2 != nullptr) {
-            if constexpr (V == 4) *reinterpret_cast<uchar4*>(pseudo2 + n) = make_uchar4((uint8_t)am2[0], (uint8_t)am2[1], (uint8_t)am2[2], (uint8_t)am2[3]);
-            else pseudo2[n] = (uint8_t)am2[0];
-        }
+        if (pseudo1 != nullptr) store_bytes<V>(pseudo1, n, am1);
+        if (pseudo2 != nullptr) store_bytes<V>(pseudo2, n, am2);
         fwd_one<C, V>(a, y, am2, lab, ce_y[0], ce_x[0], A[0], IY[0], IX[0]);
         fwd_one<C, V>(b, y, am1, lab, ce_y[1], ce_x[1], A[1], IY[1], IX[1]);
 #pragma unroll
@@ -119,27 +110,20 @@ __global__ __launch_bounds__(kThreads) void cps_fwd_kernel(const float* __restri
             }
     }
     // wave sums by shuffles, one LDS round over the block's waves, one partial row per block
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    auto put = [&](int col, float v) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) red[wave][col] = v;
-    };
-    put(0, ce_y[0]); put(1, ce_y[1]); put(2, ce_x[0]); put(3, ce_x[1]); put(4, bad);
+    const PartialRow<kCols> row{red};
+    row.put(0, ce_y[0]); row.put(1, ce_y[1]); row.put(2, ce_x[0]); row.put(3, ce_x[1]); row.put(4, bad);
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-        put(col_ny(C, c), NY[c]);
+        row.put(col_ny(C, c), NY[c]);
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-            put(col_a(C, m, c), A[m][c]);
-            put(col_iy(C, m, c), IY[m][c]);
-            put(col_ix(C, m, c), IX[m][c]);
-            put(col_np(C, m, c), NP[m][c]);
+            row.put(col_a(C, m, c), A[m][c]);
+            row.put(col_iy(C, m, c), IY[m][c]);
+            row.put(col_ix(C, m, c), IX[m][c]);
+            row.put(col_np(C, m, c), NP[m][c]);
         }
     }
-    __syncthreads();
-    if (threadIdx.x < n_cols(C))
-        partials[(long)blockIdx.x * kCols + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    row.store(n_cols(C), partials);
 }
 
 // The six terms t (scalar layout: include/uaps_hip.h, UAPS_CPS_S_*): network m(t) = t & 1 on rows rows(t) against target tgt(t)
@@ -153,14 +137,8 @@ __global__ __launch_bounds__(128) void cps_finalize(const float* __restrict__ pa
     __shared__ double sum[2][kCols];
     __shared__ double dice_part[6][C];
     const int t = threadIdx.x;
-    if (t < n_cols(C)) {
-        for (int h = 0; h < 2; ++h) {
-            const int b0 = h ? gl : 0, b1 = h ? gl + gu : gl;
-            double acc = 0.0;
-            for (int i = b0; i < b1; ++i) acc += (double)partials[(long)i * kCols + t];
-            sum[h][t] = acc;
-        }
-    }
+    column_sums<kCols>(partials, 0, gl, n_cols(C), sum[0]);
+    column_sums<kCols>(partials, gl, gl + gu, n_cols(C), sum[1]);
     __syncthreads();
     if (t < 6 * C) {
         const int term = t / C, c = t - term * C, m = term & 1, h = term >= 4;
@@ -259,28 +237,21 @@ __global__ __launch_bounds__(kThreads) void cps_bwd_kernel(const float* __restri
     }
 }
 
-inline int grid_for(long n) { long g = (n + kThreads - 1) / kThreads; return (int)(g > kMaxBlocks ? kMaxBlocks : (g < 1 ? 1 : g)); }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
 Split split_for(int N, int B_lab, long HW, int V) {
     Split sp{};
     sp.HW = HW;
     sp.B_lab = B_lab;
     sp.items_l = (long)B_lab * HW / V;
     sp.items_u = (long)(N - B_lab) * HW / V;
-    sp.gl = grid_for(sp.items_l);
-    sp.gu = grid_for(sp.items_u);
+    sp.gl = grid_for(sp.items_l, kMaxBlocks);
+    sp.gu = grid_for(sp.items_u, kMaxBlocks);
     return sp;
 }
 
 template <int C> int run_fwd(bool vec, const float* z1, const float* z2, const long long* labels, int N, int B_lab, long HW, double eps,
                              uint8_t* p1, uint8_t* p2, float* scalars, float* partials, hipStream_t st) {
     const Split sp = split_for(N, B_lab, HW, vec ? 4 : 1);
-    if (vec)
-        UAPS_LAUNCH_MAIN((cps_fwd_kernel<C, 4>), dim3(sp.gl + sp.gu), dim3(kThreads), 0, st, z1, z2, labels, sp, p1, p2, partials);
-    else
-        UAPS_LAUNCH_MAIN((cps_fwd_kernel<C, 1>), dim3(sp.gl + sp.gu), dim3(kThreads), 0, st, z1, z2, labels, sp, p1, p2, partials);
+    UAPS_LAUNCH_V(vec, cps_fwd_kernel, C, sp.gl + sp.gu, st, z1, z2, labels, sp, p1, p2, partials);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((cps_finalize<C>), dim3(1), dim3(128), 0, st, (const float*)partials, sp.gl, sp.gu, (double)B_lab * HW,
@@ -292,18 +263,9 @@ template <int C> int run_bwd(bool vec, const float* z1, const float* z2, const l
                              const float* g_lcps, const float* g_cps, int N, int B_lab, long HW, float* dz1, float* dz2, hipStream_t st) {
     const Split sp = split_for(N, B_lab, HW, vec ? 4 : 1);
     const float inv_nl = (float)(1.0 / ((double)B_lab * HW)), inv_nu = (float)(1.0 / ((double)(N - B_lab) * HW));
-    if (vec)
-        UAPS_LAUNCH_MAIN((cps_bwd_kernel<C, 4>), dim3(sp.gl + sp.gu), dim3(kThreads), 0, st, z1, z2, labels, scalars, g_sup, g_lcps, g_cps, sp,
-                         inv_nl, inv_nu, dz1, dz2);
-    else
-        UAPS_LAUNCH_MAIN((cps_bwd_kernel<C, 1>), dim3(sp.gl + sp.gu), dim3(kThreads), 0, st, z1, z2, labels, scalars, g_sup, g_lcps, g_cps, sp,
-                         inv_nl, inv_nu, dz1, dz2);
+    UAPS_LAUNCH_V(vec, cps_bwd_kernel, C, sp.gl + sp.gu, st, z1, z2, labels, scalars, g_sup, g_lcps, g_cps, sp, inv_nl, inv_nu, dz1, dz2);
     return (int)hipGetLastError();
 }
-
-#define UAPS_BY_C(C, CALL) \
-    switch (C) { case 2: return CALL(2); case 3: return CALL(3); case 4: return CALL(4); case 5: return CALL(5); \
-                 case 6: return CALL(6); case 7: return CALL(7); case 8: return CALL(8); default: return UAPS_ERANGE; }
 
 // rows [0, B_lab) labelled and [B_lab, N) unlabelled, both non-empty (the reference's means over an empty row set are NaN)
 int check_shape(int N, int B_lab, int C, int H, int W) {

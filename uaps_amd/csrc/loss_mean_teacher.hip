@@ -11,12 +11,11 @@
 #include <math.h>
 #include "../../include/uaps_hip.h"
 #include "philox.hpp"
-#include "hints.hpp"
+#include "loss_common.hpp"
 
 namespace {
-constexpr int kThreads = 256;
+using namespace uaps::loss;
 constexpr int kMaxBlocks = 1024;
-constexpr double kTooBig = 2147483648.0;      // bytes: every tensor an entry point takes stays below 2 GiB
 
 // ---- EMA update: one launch over up to kEmaBatch tensors; block b handles chunk b of the flat chunk table ---------------------
 constexpr int kEmaBatch = 128;
@@ -102,22 +101,13 @@ template <int C> __device__ __forceinline__ void softmax_p(const float (&z)[C], 
     for (int c = 0; c < C; ++c) p[c] = p[c] / s;
 }
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();                                  // red is reused by the second sum of the block
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // T > 0: mc = raw teacher logits [T][B][C][H][W]; T == 0: mc = mean probabilities [B][C][H][W]; mc == nullptr: MT mode (no mask).
 // partials[2 b] = sum m d, partials[2 b + 1] = sum m over the pixels of block b.
 template <int C>
 __global__ __launch_bounds__(kThreads) void mc_fwd_kernel(const float* __restrict__ s, const float* __restrict__ e,
                                                           const float* __restrict__ mc, int T, long HW, long N, float threshold,
                                                           uint8_t* __restrict__ mask, float* __restrict__ unc, float* __restrict__ partials) {
-    __shared__ float red[kThreads / 64];
+    __shared__ float red[kWaves];
     float acc_md = 0.f, acc_m = 0.f;
     const long plane = N * C;                         // one MC pass: B C H W floats
     const float invT = T > 0 ? 1.f / (float)T : 1.f;
@@ -201,8 +191,6 @@ __global__ __launch_bounds__(kThreads) void mc_bwd_kernel(const float* __restric
     }
 }
 
-inline int grid_for(long n) { long g = (n + kThreads - 1) / kThreads; return (int)(g > kMaxBlocks ? kMaxBlocks : (g < 1 ? 1 : g)); }
-
 template <int C> int run_fwd(const float* s, const float* e, const float* mc, int T, long HW, long N, float thr, uint8_t* mask, float* unc,
                              float* partials, int grid, hipStream_t st) {
     UAPS_LAUNCH_MAIN((mc_fwd_kernel<C>), dim3(grid), dim3(kThreads), 0, st, s, e, mc, T, HW, N, thr, mask, unc, partials);
@@ -213,9 +201,6 @@ template <int C> int run_bwd(const float* s, const float* e, const uint8_t* mask
     UAPS_LAUNCH_MAIN((mc_bwd_kernel<C>), dim3(grid), dim3(kThreads), 0, st, s, e, mask, g, sums, inv_norm, HW, N, ds);
     return (int)hipGetLastError();
 }
-#define UAPS_BY_C(C, CALL) \
-    switch (C) { case 2: return CALL(2); case 3: return CALL(3); case 4: return CALL(4); case 5: return CALL(5); \
-                 case 6: return CALL(6); case 7: return CALL(7); case 8: return CALL(8); default: return UAPS_ERANGE; }
 }  // namespace
 
 extern "C" int uaps_ema_update(float* const* ema_host, const float* const* param_host, const long* numel_host, int n, float alpha,
@@ -254,13 +239,12 @@ static int teacher_noise_impl(const float* x, const float* noise, int B, int Cin
                                        reinterpret_cast<uintptr_t>(noise)) & 15) == 0;
     const long total4 = (total + 3) / 4;
     uaps::account_bytes(4.0 * (total + (double)B * chw) + (noise ? 4.0 * total : 0.0));
-    long grid = (total4 + kThreads - 1) / kThreads;
-    if (grid > 4096) grid = 4096;
+    const int grid = grid_for(total4, 4096);
     if (noise)
-        UAPS_LAUNCH_MAIN(teacher_noise_kernel<false>, dim3((unsigned)grid), dim3(kThreads), 0, (hipStream_t)stream, x, noise, chw, (long)B,
+        UAPS_LAUNCH_MAIN(teacher_noise_kernel<false>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, x, noise, chw, (long)B,
                            total4, total, seed, offset, out, vec);
     else
-        UAPS_LAUNCH_MAIN(teacher_noise_kernel<true>, dim3((unsigned)grid), dim3(kThreads), 0, (hipStream_t)stream, x, noise, chw, (long)B,
+        UAPS_LAUNCH_MAIN(teacher_noise_kernel<true>, dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, x, noise, chw, (long)B,
                            total4, total, seed, offset, out, vec);
     return (int)hipGetLastError();
 }
@@ -300,7 +284,7 @@ extern "C" int uaps_mc_consistency_fwd(const float* student, const float* teache
     if (4.0 * (double)N * C * (T > 1 ? T : 1) >= kTooBig) return UAPS_ERANGE;
     if (!workspace || workspace_bytes < (size_t)kMaxBlocks * 2 * sizeof(float)) return UAPS_EWORKSPACE;
     uaps::account_bytes(4.0 * N * C * (2 + (mc ? (T > 0 ? T : 1) : 0)) + (mc ? N : 0) + (uncertainty ? 4.0 * N : 0.0));
-    const int grid = grid_for(N);
+    const int grid = grid_for(N, kMaxBlocks);
     hipStream_t st = (hipStream_t)stream;
     const int rc = fwd_dispatch(C, student, teacher, mc, T, HW, N, threshold, mask, uncertainty, (float*)workspace, grid, st);
     if (rc) return rc;
@@ -323,6 +307,6 @@ extern "C" int uaps_mc_consistency_bwd(const float* student, const float* teache
     const long HW = (long)H * W, N = (long)B * HW;
     if (4.0 * (double)N * C >= kTooBig) return UAPS_ERANGE;
     uaps::account_bytes(4.0 * N * C * 3 + (mask ? N : 0));
-    return bwd_dispatch(C, student, teacher, mask, grad, out3, (float)(1.0 / ((double)N * C)), HW, N, dstudent, grid_for(N),
+    return bwd_dispatch(C, student, teacher, mask, grad, out3, (float)(1.0 / ((double)N * C)), HW, N, dstudent, grid_for(N, kMaxBlocks),
                         (hipStream_t)stream);
 }

@@ -15,16 +15,13 @@
 #include <string.h>
 #include <math.h>
 #include "../../include/uaps_hip.h"
-#include "hints.hpp"
-#include "loss_pixel.hpp"
+#include "loss_common.hpp"
 
 namespace {
+using namespace uaps::loss;
 using namespace uaps::pixel;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
 constexpr int kMaxBlocks = 1024;
 constexpr int kCols = 40;                      // floats of a block's partial row: 5 + 4 C used (37 at C = 8)
-constexpr double kTooBig = 2147483648.0;       // bytes: every tensor an entry point takes stays below 2 GiB
 
 // columns of a partial row
 //   0  sum w_y nll     1  sum w_y     2  sum a_y (1 - p_y)^gamma nll     3  valid pixels     4  labels outside [0, C), not ignored
@@ -39,12 +36,7 @@ __host__ __device__ constexpr int n_cols(int C) { return 5 + 4 * C; }
 template <int C, int V>
 __device__ __forceinline__ float load_labels_ignore(const long long* __restrict__ labels, long n, long long ignore, int (&y)[V]) {
     long long t[V];
-    if constexpr (V == 4) {
-        const longlong2 t0 = *reinterpret_cast<const longlong2*>(labels + n), t1 = *reinterpret_cast<const longlong2*>(labels + n + 2);
-        t[0] = t0.x; t[1] = t0.y; t[2] = t1.x; t[3] = t1.y;
-    } else {
-        t[0] = labels[n];
-    }
+    load_raw_labels<V>(labels, n, t);
     float bad = 0.f;
 #pragma unroll
     for (int v = 0; v < V; ++v) {
@@ -117,18 +109,11 @@ __global__ __launch_bounds__(kThreads) void seg_fwd_kernel(const float* __restri
             }
     }
     // wave sums by shuffles, one LDS round over the block's waves, one partial row per block
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    auto put = [&](int col, float v) {
+    const PartialRow<kCols> row{red};
+    row.put(0, ce); row.put(1, ws); row.put(2, fs); row.put(3, nv); row.put(4, bad);
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) red[wave][col] = v;
-    };
-    put(0, ce); put(1, ws); put(2, fs); put(3, nv); put(4, bad);
-#pragma unroll
-    for (int c = 0; c < C; ++c) { put(col_a(C, c), A[c]); put(col_i(C, c), I[c]); put(col_n(C, c), N[c]); put(col_z(C, c), Z[c]); }
-    __syncthreads();
-    if (threadIdx.x < n_cols(C))
-        partials[(long)blockIdx.x * kCols + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    for (int c = 0; c < C; ++c) { row.put(col_a(C, c), A[c]); row.put(col_i(C, c), I[c]); row.put(col_n(C, c), N[c]); row.put(col_z(C, c), Z[c]); }
+    row.store(n_cols(C), partials);
 }
 
 // Column sums over the blocks in double, in block order; then per class the selected region terms' parts and the factors of the
@@ -144,11 +129,7 @@ __global__ __launch_bounds__(64) void seg_finalize(const float* __restrict__ par
     __shared__ double sum[kCols];
     __shared__ double part[4][C];              // per class f_c of dice, jaccard, tversky and v_c (1 - f_c) of dice_sq
     const int t = threadIdx.x;
-    if (t < n_cols(C)) {
-        double acc = 0.0;
-        for (int i = 0; i < blocks; ++i) acc += (double)partials[(long)i * kCols + t];
-        sum[t] = acc;
-    }
+    column_sums<kCols>(partials, 0, blocks, n_cols(C), sum);
     __syncthreads();
     if (t < C) {
         const double A = sum[col_a(C, t)], I = sum[col_i(C, t)], N = sum[col_n(C, t)], Zs = sum[col_z(C, t)];
@@ -276,17 +257,11 @@ __global__ __launch_bounds__(kThreads) void seg_bwd_kernel(const float* __restri
     }
 }
 
-inline int grid_for(long n) { long g = (n + kThreads - 1) / kThreads; return (int)(g > kMaxBlocks ? kMaxBlocks : (g < 1 ? 1 : g)); }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 template <int C> int run_fwd(bool vec, const float* z, const long long* labels, const uaps_segloss_params& prm, int B, long HW,
                              float* scalars, float* partials, hipStream_t st) {
     const long items = (long)B * HW / (vec ? 4 : 1);
-    const int grid = grid_for(items);
-    if (vec)
-        UAPS_LAUNCH_MAIN((seg_fwd_kernel<C, 4>), dim3(grid), dim3(kThreads), 0, st, z, labels, prm, HW, items, partials);
-    else
-        UAPS_LAUNCH_MAIN((seg_fwd_kernel<C, 1>), dim3(grid), dim3(kThreads), 0, st, z, labels, prm, HW, items, partials);
+    const int grid = grid_for(items, kMaxBlocks);
+    UAPS_LAUNCH_V(vec, seg_fwd_kernel, C, grid, st, z, labels, prm, HW, items, partials);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((seg_finalize<C>), dim3(1), dim3(64), 0, st, (const float*)partials, grid, prm, scalars);
@@ -296,17 +271,9 @@ template <int C> int run_fwd(bool vec, const float* z, const long long* labels, 
 template <int C> int run_bwd(bool vec, const float* z, const long long* labels, const uaps_segloss_params& prm, const float* scalars,
                              const float* grad, int B, long HW, float* dz, hipStream_t st) {
     const long items = (long)B * HW / (vec ? 4 : 1);
-    const int grid = grid_for(items);
-    if (vec)
-        UAPS_LAUNCH_MAIN((seg_bwd_kernel<C, 4>), dim3(grid), dim3(kThreads), 0, st, z, labels, prm, scalars, grad, HW, items, dz);
-    else
-        UAPS_LAUNCH_MAIN((seg_bwd_kernel<C, 1>), dim3(grid), dim3(kThreads), 0, st, z, labels, prm, scalars, grad, HW, items, dz);
+    UAPS_LAUNCH_V(vec, seg_bwd_kernel, C, grid_for(items, kMaxBlocks), st, z, labels, prm, scalars, grad, HW, items, dz);
     return (int)hipGetLastError();
 }
-
-#define UAPS_BY_C(C, CALL) \
-    switch (C) { case 2: return CALL(2); case 3: return CALL(3); case 4: return CALL(4); case 5: return CALL(5); \
-                 case 6: return CALL(6); case 7: return CALL(7); case 8: return CALL(8); default: return UAPS_ERANGE; }
 
 int check_shape(int B, int C, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return UAPS_EINVAL;

@@ -3,7 +3,7 @@
 //   uaps_ucc_cutmix_batch   [mix(x_l) ; crossmix(x_wk) ; crossmix(x_st)] + the mixed labels + max|.|       cross_cutmix.py:78-123
 //   uaps_ucc_fwd            4 CE + 4 Dice terms, the two KL variance means and exp(-variance) means, sup, ps_1, ps_2, ps   :186-240
 //   uaps_ucc_bwd            d(g_sup sup + g_ps ps) / dz for every row of both tensors
-// The loss kernels follow loss_cps.hip (the per-pixel helpers are shared: loss_pixel.hpp): a lane owns a pixel of image i (four
+// The loss kernels follow loss_cps.hip (the per-pixel helpers are shared: loss_common.hpp): a lane owns a pixel of image i (four
 // consecutive pixels when the plane is a multiple of 4 floats and the pointers are 16-byte aligned) and walks the three row blocks
 // of that pixel as three PAIRS of logit vectors -- (z1, z2) labelled, (z1_wk, z2_st) = variance_1 and head 2's pseudo-supervised
 // term, (z1_st, z2_wk) = variance_2 and head 1's -- so that only two vectors are live at a time and every logit is read once by the
@@ -14,16 +14,13 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/uaps_hip.h"
-#include "hints.hpp"
-#include "loss_pixel.hpp"
+#include "loss_common.hpp"
 
 namespace {
+using namespace uaps::loss;
 using namespace uaps::pixel;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
 constexpr int kMaxBlocks = 1024;
 constexpr int kCols = 100;                     // floats of a block's partial row: 9 + 11 C used (97 at C = 8)
-constexpr double kTooBig = 2147483648.0;       // bytes: every tensor an entry point takes stays below 2 GiB
 
 // columns of a partial row; term t: 0, 1 = head 1, 2 against the ground truth; 2 = z1_st against pseudo_1; 3 = z2_st against pseudo_2
 //   [0, 4)   CE sum of term t          4   labels outside [0, C)
@@ -128,11 +125,6 @@ __device__ __forceinline__ void kl_pair(float (&a)[C][V], float (&b)[C][V], floa
 }
 
 template <int V>
-__device__ __forceinline__ void store_bytes(uint8_t* __restrict__ dst, long n, const int (&am)[V]) {
-    if constexpr (V == 4) *reinterpret_cast<uchar4*>(dst + n) = make_uchar4((uint8_t)am[0], (uint8_t)am[1], (uint8_t)am[2], (uint8_t)am[3]);
-    else dst[n] = (uint8_t)am[0];
-}
-template <int V>
 __device__ __forceinline__ void store_floats(float* __restrict__ dst, long n, const float (&x)[V]) {
     if constexpr (V == 4) *reinterpret_cast<float4*>(dst + n) = make_float4(x[0], x[1], x[2], x[3]);
     else dst[n] = x[0];
@@ -205,24 +197,17 @@ __global__ __launch_bounds__(kThreads) void ucc_fwd_kernel(const float* __restri
         }
     }
     // wave sums by shuffles, one LDS round over the block's waves, one partial row per block
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    auto put = [&](int col, float v) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) red[wave][col] = v;
-    };
-    put(0, ce[0]); put(1, ce[1]); put(2, ce[2]); put(3, ce[3]); put(4, bad);
-    put(5, sv[0]); put(6, se[0]); put(7, sv[1]); put(8, se[1]);
+    const PartialRow<kCols> row{red};
+    row.put(0, ce[0]); row.put(1, ce[1]); row.put(2, ce[2]); row.put(3, ce[3]); row.put(4, bad);
+    row.put(5, sv[0]); row.put(6, se[0]); row.put(7, sv[1]); row.put(8, se[1]);
 #pragma unroll
     for (int c = 0; c < C; ++c) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) { put(col_a(C, t, c), A[t][c]); put(col_i(C, t, c), I[t][c]); }
+        for (int t = 0; t < 4; ++t) { row.put(col_a(C, t, c), A[t][c]); row.put(col_i(C, t, c), I[t][c]); }
 #pragma unroll
-        for (int k = 0; k < 3; ++k) put(col_n(C, k, c), N[k][c]);
+        for (int k = 0; k < 3; ++k) row.put(col_n(C, k, c), N[k][c]);
     }
-    __syncthreads();
-    if (threadIdx.x < n_cols(C))
-        partials[(long)blockIdx.x * kCols + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    row.store(n_cols(C), partials);
 }
 
 // Column sums over the blocks in double, in block order; then per term and class (scalar layout: include/uaps_hip.h, UAPS_UCC_S_*)
@@ -233,11 +218,7 @@ __global__ __launch_bounds__(128) void ucc_finalize(const float* __restrict__ pa
     __shared__ double sum[kCols];
     __shared__ double dice_part[4][C];
     const int t = threadIdx.x;
-    if (t < n_cols(C)) {
-        double acc = 0.0;
-        for (int i = 0; i < blocks; ++i) acc += (double)partials[(long)i * kCols + t];
-        sum[t] = acc;
-    }
+    column_sums<kCols>(partials, 0, blocks, n_cols(C), sum);
     __syncthreads();
     if (t < 4 * C) {
         const int term = t / C, c = t - term * C;
@@ -358,18 +339,11 @@ __global__ __launch_bounds__(kThreads) void ucc_bwd_kernel(const float* __restri
     }
 }
 
-inline int grid_for(long n) { long g = (n + kThreads - 1) / kThreads; return (int)(g > kMaxBlocks ? kMaxBlocks : (g < 1 ? 1 : g)); }
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
 template <int C> int run_fwd(bool vec, const float* z1, const float* z2, const long long* labels, int B, long HW, double eps, uint8_t* p1,
                              uint8_t* p2, float* v1, float* v2, float* scalars, float* partials, hipStream_t st) {
     const long items = (long)B * HW / (vec ? 4 : 1);
-    const int grid = grid_for(items);
-    if (vec)
-        UAPS_LAUNCH_MAIN((ucc_fwd_kernel<C, 4>), dim3(grid), dim3(kThreads), 0, st, z1, z2, labels, B, HW, items, p1, p2, v1, v2, partials);
-    else
-        UAPS_LAUNCH_MAIN((ucc_fwd_kernel<C, 1>), dim3(grid), dim3(kThreads), 0, st, z1, z2, labels, B, HW, items, p1, p2, v1, v2, partials);
+    const int grid = grid_for(items, kMaxBlocks);
+    UAPS_LAUNCH_V(vec, ucc_fwd_kernel, C, grid, st, z1, z2, labels, B, HW, items, p1, p2, v1, v2, partials);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((ucc_finalize<C>), dim3(1), dim3(128), 0, st, (const float*)partials, grid, (double)B * HW, eps, scalars);
@@ -379,20 +353,10 @@ template <int C> int run_fwd(bool vec, const float* z1, const float* z2, const l
 template <int C> int run_bwd(bool vec, const float* z1, const float* z2, const long long* labels, const float* scalars, const float* g_sup,
                              const float* g_ps, int B, long HW, float* dz1, float* dz2, hipStream_t st) {
     const long items = (long)B * HW / (vec ? 4 : 1);
-    const int grid = grid_for(items);
     const float inv_n = (float)(1.0 / ((double)B * HW));
-    if (vec)
-        UAPS_LAUNCH_MAIN((ucc_bwd_kernel<C, 4>), dim3(grid), dim3(kThreads), 0, st, z1, z2, labels, scalars, g_sup, g_ps, B, HW, items, inv_n,
-                         dz1, dz2);
-    else
-        UAPS_LAUNCH_MAIN((ucc_bwd_kernel<C, 1>), dim3(grid), dim3(kThreads), 0, st, z1, z2, labels, scalars, g_sup, g_ps, B, HW, items, inv_n,
-                         dz1, dz2);
+    UAPS_LAUNCH_V(vec, ucc_bwd_kernel, C, grid_for(items, kMaxBlocks), st, z1, z2, labels, scalars, g_sup, g_ps, B, HW, items, inv_n, dz1, dz2);
     return (int)hipGetLastError();
 }
-
-#define UAPS_BY_C(C, CALL) \
-    switch (C) { case 2: return CALL(2); case 3: return CALL(3); case 4: return CALL(4); case 5: return CALL(5); \
-                 case 6: return CALL(6); case 7: return CALL(7); case 8: return CALL(8); default: return UAPS_ERANGE; }
 
 // z1, z2: [3B, C, H, W]
 int check_shape(int B, int C, int H, int W) {
@@ -428,13 +392,12 @@ int cutmix_impl(float* amax, const float* x_l, const float* x_wk, const float* x
     uaps::account_bytes(4.0 * 6.0 * n + 16.0 * B * HW);      // three batches read, three written; the labels read and written
     const bool vec = HW % 4 == 0 && al16(x_l) && al16(x_wk) && al16(x_st) && al16(out);
     const long items = n / (vec ? 4 : 1);
-    long grid = (items + kThreads - 1) / kThreads;
-    if (grid > 4096) grid = 4096;
+    const int grid = grid_for(items, 4096);
     if (vec)
-        UAPS_LAUNCH_MAIN((ucc_cutmix_kernel<4>), dim3((unsigned)grid), dim3(kThreads), 0, (hipStream_t)stream, x_l, x_wk, x_st,
+        UAPS_LAUNCH_MAIN((ucc_cutmix_kernel<4>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, x_l, x_wk, x_st,
                          (const long long*)y_l, rc, B, Cin, W, HW, items, out, (long long*)y_out, amax);
     else
-        UAPS_LAUNCH_MAIN((ucc_cutmix_kernel<1>), dim3((unsigned)grid), dim3(kThreads), 0, (hipStream_t)stream, x_l, x_wk, x_st,
+        UAPS_LAUNCH_MAIN((ucc_cutmix_kernel<1>), dim3(grid), dim3(kThreads), 0, (hipStream_t)stream, x_l, x_wk, x_st,
                          (const long long*)y_l, rc, B, Cin, W, HW, items, out, (long long*)y_out, amax);
     return (int)hipGetLastError();
 }

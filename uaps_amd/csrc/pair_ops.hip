@@ -11,10 +11,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/uaps_hip.h"
-#include "hints.hpp"
+#include "loss_common.hpp"
 
 namespace {
-constexpr int kThreads = 256;
+using namespace uaps::loss;
 constexpr int kMaxBlocks = 1024;
 
 template <int C> __device__ __forceinline__ void softmax_c(const float (&z)[C], float (&p)[C], float (&lp)[C]) {
@@ -29,8 +29,10 @@ template <int C> __device__ __forceinline__ void softmax_c(const float (&z)[C], 
     for (int c = 0; c < C; ++c) { p[c] *= inv; lp[c] = z[c] - lse; }
 }
 
+// Not loss::block_sum: a kernel here forms ONE sum, so this form owns its LDS and has no barrier in front of the write (the shared
+// one has it for a second sum of the block); the shuffle order and the (r0 + r1) + (r2 + r3) association are the same.
 __device__ __forceinline__ float block_sum(float v) {
-    __shared__ float red[kThreads / 64];
+    __shared__ float red[kWaves];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -154,8 +156,6 @@ __global__ __launch_bounds__(kThreads) void entropy_kernel(const float* __restri
     }
 }
 
-inline int grid_for(long n) { long g = (n + kThreads - 1) / kThreads; return (int)(g > kMaxBlocks ? kMaxBlocks : (g < 1 ? 1 : g)); }
-
 template <int C> int run_fwd(bool probs, const float* a, const float* b, long HW, long N, float* mse, float* klmap, float* partials,
                              int grid, hipStream_t s) {
     if (probs) hipLaunchKernelGGL((pair_fwd_kernel<C, true>), dim3(grid), dim3(kThreads), 0, s, a, b, HW, N, mse, klmap, partials);
@@ -177,9 +177,6 @@ template <int C> int run_ent(const float* p, long HW, long N, float* ent, float*
     hipLaunchKernelGGL((entropy_kernel<C>), dim3(grid), dim3(kThreads), 0, s, p, HW, N, ent, partials);
     return (int)hipGetLastError();
 }
-#define UAPS_BY_C(C, CALL) \
-    switch (C) { case 2: return CALL(2); case 3: return CALL(3); case 4: return CALL(4); case 5: return CALL(5); \
-                 case 6: return CALL(6); case 7: return CALL(7); case 8: return CALL(8); default: return UAPS_ERANGE; }
 }  // namespace
 
 extern "C" int uaps_pair_workspace_bytes(size_t* out) {
@@ -201,7 +198,7 @@ extern "C" int uaps_softmax_pair_fwd(const float* a, const float* b, int probs, 
     if (C < 2 || C > UAPS_MAX_CLASSES) return UAPS_ERANGE;
     if (kl_mean && (!ws || ws_bytes < (size_t)kMaxBlocks * sizeof(float))) return UAPS_EWORKSPACE;
     const long HW = (long)H * W, N = (long)B * HW;
-    const int grid = grid_for(N);
+    const int grid = grid_for(N, kMaxBlocks);
     hipStream_t s = (hipStream_t)stream;
     const int rc = pair_fwd_dispatch(C, probs != 0, a, b, HW, N, mse_map, kl_map, kl_mean ? (float*)ws : nullptr, grid, s);
     if (rc || !kl_mean) return rc;
@@ -221,7 +218,7 @@ extern "C" int uaps_softmax_mse_bwd(const float* a, const float* b, const float*
     if (!a || !b || !grad_map || !da || B <= 0 || H <= 0 || W <= 0) return UAPS_EINVAL;
     if (C < 2 || C > UAPS_MAX_CLASSES) return UAPS_ERANGE;
     const long HW = (long)H * W, N = (long)B * HW;
-    return pair_bwd_dispatch(C, true, a, b, grad_map, nullptr, 1.f, HW, N, da, grid_for(N), (hipStream_t)stream);
+    return pair_bwd_dispatch(C, true, a, b, grad_map, nullptr, 1.f, HW, N, da, grid_for(N, kMaxBlocks), (hipStream_t)stream);
 }
 
 extern "C" int uaps_softmax_kl_bwd(const float* a, const float* b, const float* gscalar, int B, int C, int H, int W, float* da,
@@ -229,7 +226,7 @@ extern "C" int uaps_softmax_kl_bwd(const float* a, const float* b, const float* 
     if (!a || !b || !da || B <= 0 || H <= 0 || W <= 0) return UAPS_EINVAL;
     if (C < 2 || C > UAPS_MAX_CLASSES) return UAPS_ERANGE;
     const long HW = (long)H * W, N = (long)B * HW;
-    return pair_bwd_dispatch(C, false, a, b, nullptr, gscalar, (float)(1.0 / ((double)N * C)), HW, N, da, grid_for(N), (hipStream_t)stream);
+    return pair_bwd_dispatch(C, false, a, b, nullptr, gscalar, (float)(1.0 / ((double)N * C)), HW, N, da, grid_for(N, kMaxBlocks), (hipStream_t)stream);
 }
 
 static int klmap_bwd_dispatch(int C, const float* a, const float* b, const float* gmap, long HW, long N, float* da, float* db, int grid,
@@ -244,7 +241,7 @@ extern "C" int uaps_softmax_klmap_bwd(const float* a, const float* b, const floa
     if (!a || !b || !grad_map || (!da && !db) || B <= 0 || H <= 0 || W <= 0) return UAPS_EINVAL;
     if (C < 2 || C > UAPS_MAX_CLASSES) return UAPS_ERANGE;
     const long HW = (long)H * W, N = (long)B * HW;
-    return klmap_bwd_dispatch(C, a, b, grad_map, HW, N, da, db, grid_for(N), (hipStream_t)stream);
+    return klmap_bwd_dispatch(C, a, b, grad_map, HW, N, da, db, grid_for(N, kMaxBlocks), (hipStream_t)stream);
 }
 
 static int ent_dispatch(int C, const float* p, long HW, long N, float* ent, float* partials, int grid, hipStream_t s) {
@@ -259,7 +256,7 @@ extern "C" int uaps_entropy_map(const float* p, int B, int C, int H, int W, floa
     if (C < 2 || C > UAPS_MAX_CLASSES) return UAPS_ERANGE;
     if (ent_mean && (!ws || ws_bytes < (size_t)kMaxBlocks * sizeof(float))) return UAPS_EWORKSPACE;
     const long HW = (long)H * W, N = (long)B * HW;
-    const int grid = grid_for(N);
+    const int grid = grid_for(N, kMaxBlocks);
     hipStream_t s = (hipStream_t)stream;
     const int rc = ent_dispatch(C, p, HW, N, ent_map, ent_mean ? (float*)ws : nullptr, grid, s);
     if (rc || !ent_mean) return rc;
@@ -333,7 +330,6 @@ __global__ __launch_bounds__(kThreads) void cat2_amax_kernel(const float* __rest
         }
     if (amax != nullptr) uaps::block_amax_to(amax, m, s16);
 }
-inline bool al16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 }  // namespace
 
 // The two batches of a training step as one (UAPS_train.py:177 + :185 run as one pass, unet.UNet_UAPS.forward_pair): out [2n] =
@@ -351,8 +347,8 @@ extern "C" int uaps_cat2_h(const uaps_call_hints* hints, const float* a, const f
 static int cat2_impl(float* amax, const float* a, const float* b, float* out, long n, uaps_stream_t stream) {
     if (!a || !b || !out || n <= 0) return UAPS_EINVAL;
     uaps::account_bytes(16.0 * n);                        // both halves read, the joined batch written
-    const long n4 = (al16p(a) && al16p(b) && al16p(out) && n % 4 == 0) ? n / 4 : 0;
-    hipLaunchKernelGGL(cat2_amax_kernel, dim3(grid_for(n4 > 0 ? 2 * n4 : 1)), dim3(kThreads), 0, (hipStream_t)stream, a, b, out, n4, n, amax);
+    const long n4 = (al16(a) && al16(b) && al16(out) && n % 4 == 0) ? n / 4 : 0;
+    hipLaunchKernelGGL(cat2_amax_kernel, dim3(grid_for(n4 > 0 ? 2 * n4 : 1, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream, a, b, out, n4, n, amax);
     return (int)hipGetLastError();
 }
 
@@ -360,10 +356,10 @@ extern "C" int uaps_relu_bwd_sum(const float* const* dout_host, int k, const flo
     if (!dout_host || k < 1 || k > kReluBwdMax || !out || !dx || n <= 0) return UAPS_EINVAL;
     ReluBwdIn in{};
     in.k = k;
-    bool al = al16p(out) && al16p(dx);
-    for (int i = 0; i < k; ++i) { if (!dout_host[i]) return UAPS_EINVAL; in.g[i] = dout_host[i]; al = al && al16p(dout_host[i]); }
+    bool al = al16(out) && al16(dx);
+    for (int i = 0; i < k; ++i) { if (!dout_host[i]) return UAPS_EINVAL; in.g[i] = dout_host[i]; al = al && al16(dout_host[i]); }
     const long n4 = al ? n / 4 : 0;
-    hipLaunchKernelGGL(relu_bwd_sum_kernel, dim3(grid_for(n4 > 0 ? n4 : 1)), dim3(kThreads), 0, (hipStream_t)stream, in, out, dx, n4, n);
+    hipLaunchKernelGGL(relu_bwd_sum_kernel, dim3(grid_for(n4 > 0 ? n4 : 1, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream, in, out, dx, n4, n);
     return (int)hipGetLastError();
 }
 
@@ -377,14 +373,14 @@ extern "C" int uaps_add_relu_h(const uaps_call_hints* hints, const float* a, con
 }
 static int add_relu_impl(float* amax, const float* a, const float* b, float* out, long n, uaps_stream_t stream) {
     if (!a || !b || !out || n <= 0) return UAPS_EINVAL;
-    const long n4 = (al16p(a) && al16p(b) && al16p(out)) ? n / 4 : 0;
-    hipLaunchKernelGGL(add_relu_kernel, dim3(grid_for(n4 > 0 ? n4 : 1)), dim3(kThreads), 0, (hipStream_t)stream, a, b, out, n4, n, amax);
+    const long n4 = (al16(a) && al16(b) && al16(out)) ? n / 4 : 0;
+    hipLaunchKernelGGL(add_relu_kernel, dim3(grid_for(n4 > 0 ? n4 : 1, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream, a, b, out, n4, n, amax);
     return (int)hipGetLastError();
 }
 
 extern "C" int uaps_relu_bwd(const float* dout, const float* out, float* dx, long n, uaps_stream_t stream) {
     if (!dout || !out || !dx || n <= 0) return UAPS_EINVAL;
-    const long n4 = (al16p(dout) && al16p(out) && al16p(dx)) ? n / 4 : 0;
-    hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n4 > 0 ? n4 : 1)), dim3(kThreads), 0, (hipStream_t)stream, dout, out, dx, n4, n);
+    const long n4 = (al16(dout) && al16(out) && al16(dx)) ? n / 4 : 0;
+    hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n4 > 0 ? n4 : 1, kMaxBlocks)), dim3(kThreads), 0, (hipStream_t)stream, dout, out, dx, n4, n);
     return (int)hipGetLastError();
 }

@@ -1137,6 +1137,54 @@ int uaps_pairloss_bwd_h(const uaps_call_hints* hints, const float* const* lab_lo
                         float cw2, const float* grad_scale, int D, int B, int C, int H, int W, long n_pixels_loss,
                         float* const* dlab_host, float* const* dun_host, int cfg, uaps_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Test-time augmentation (utilities/base.py:24-46, BaseNet.forward(x, tta=True)): csrc/tta.hip.  Over the scales, and per scale over
+ * {plain, horizontally flipped}, the reference resizes the batch (bilinear, align_corners=True), runs the network, takes the softmax,
+ * un-flips, resizes back to the input's size and adds: the SUM of S * (1 + flip) probability maps, fp32, accumulated left to right.
+ * The bilinear arithmetic is torch's fp32 form: r = (in - 1) / (out - 1) as a float (0 when out == 1), src = r * dst, i0 = (int) src,
+ * i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1, value = l0h * (l0w * v00 + l1w * v01) + l1h * (l0w * v10 + l1w * v11).
+ *
+ * uaps_tta_views, the input side of one scale: x [B, Cin, H, W] is read once, out [(1 + flip) B, Cin, h, w] receives the resized
+ *   batch in images 0 .. B-1 and, with flip == 1, its horizontal flip in images B .. 2B-1 (out[B + b, :, y, j] = out[b, :, y, w-1-j],
+ *   the same values stored mirrored), so that ONE forward of 2B images serves both views of the scale.
+ * uaps_tta_fold, the output side of all scales in one launch: logits[s] [(1 + flip) B, C, h[s], w[s]] are the network's outputs on the
+ *   views of scale s, plain images first.  Per output pixel and per scale, plain then flipped: the softmax over the classes of the
+ *   logits at the four source corners, mixed bilinearly, added to C running sums held in registers -- ((((p0 + f0) + p1) + f1) + ...).
+ *   The flipped half is un-flipped before its resize: the output column whose neighbours are x0, x1 reads columns w[s] - 1 - x0 and
+ *   w[s] - 1 - x1 of image B + b.  Written at the end, whichever are not NULL:
+ *     probs_sum [B, C, H, W] the sum;  mask [B, H, W] int64 its arg-max, the lowest index among equal sums;
+ *     conf [B, H, W] the largest sum / (S * (1 + flip)).
+ *   No atomics and no cross-lane sums: two runs give the same bits.  With W % 4 == 0 and 16-byte aligned outputs a lane owns four
+ *   consecutive pixels and stores 16 bytes; otherwise one pixel -- the same arithmetic per pixel either way.
+ * Both structs are size-versioned (fields are only ever appended; struct_size = sizeof of the caller's header; a larger one is accepted
+ * and what it appends is not read).  The pointer and size tables travel as kernel arguments: no copy, no synchronisation.
+ * Errors (nothing launched): UAPS_EINVAL null struct, x / out / logits[s] pointer, all three outputs NULL, non-positive dimension,
+ *   struct_size below this version's, flip outside {0, 1}; UAPS_ERANGE C outside [2, UAPS_MAX_CLASSES] (one-channel sigmoid heads
+ *   have no form here), S outside [1, UAPS_TTA_MAX_SCALES], a tensor of 2 GiB or more (by dimensions; of the outputs
+ *   only those that are not NULL count).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct uaps_tta_views_call {
+    uint32_t struct_size;
+    int32_t B, Cin, H, W, h, w, flip;
+    const float* x;                              /* [B][Cin][H][W] */
+    float* out;                                  /* [(1 + flip) B][Cin][h][w] */
+    uaps_stream_t stream;
+} uaps_tta_views_call;
+int uaps_tta_views(const uaps_tta_views_call* call);
+
+#define UAPS_TTA_MAX_SCALES 8
+typedef struct uaps_tta_fold_call {
+    uint32_t struct_size;
+    int32_t S, B, C, H, W, flip;
+    const float* logits[UAPS_TTA_MAX_SCALES];    /* device, [(flip ? 2 : 1) * B, C, h[s], w[s]], plain images first */
+    int32_t h[UAPS_TTA_MAX_SCALES], w[UAPS_TTA_MAX_SCALES];
+    float* probs_sum;                            /* [B][C][H][W] or NULL */
+    int64_t* mask;                               /* [B][H][W] or NULL */
+    float* conf;                                 /* [B][H][W] or NULL; not all three NULL */
+    uaps_stream_t stream;
+} uaps_tta_fold_call;
+int uaps_tta_fold(const uaps_tta_fold_call* call);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,9 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
                                                     one-channel sigmoid heads; the reference-named binary losses (bce_loss, FocalLoss,
                                                     JaccardLoss, BCEDiceLoss, iou, f_score, ...: utilities/losses_2.py) live in
                                                     `uaps_amd.binary_losses`, beside the softmax names above
+  predict_tta, tta_views, tta_fold, scaled_sizes, TTAResult, DEFAULT_SCALES   multi-scale + flip test-time augmentation
+                                                    (utilities/base.py:24-46, BaseNet.forward(x, tta=True)); ResUAPS.forward(x, tta=True),
+                                                    inference.evaluate(..., tta=True)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -43,6 +46,8 @@ from .binary_trainer import BinaryTrainer
 from . import binary_losses, binary_trainer
 from .pipelines import Recipe, Stage, RECIPES, ViewDraws, draw, augment_views, ArrayBatches, UCCArrayBatches
 from . import pipelines
+from .tta import predict_tta, tta_views, tta_fold, scaled_sizes, TTAResult, DEFAULT_SCALES
+from . import tta
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -157,6 +157,8 @@ SIGNATURES = {
     "uaps_sigmoid_kl_fwd": (C.c_int, [_PTR, _PTR, C.c_long, _PTR, _PTR, C.c_size_t, _PTR]),
     "uaps_sigmoid_kl_bwd": (C.c_int, [_PTR, _PTR, _PTR, C.c_long, _PTR, _PTR]),
     "uaps_bin_confusion": (C.c_int, [_PTR, _PTR] + [C.c_int] * 3 + [C.c_double, _PTR, _PTR]),
+    "uaps_tta_views": (C.c_int, [_PTR]),
+    "uaps_tta_fold": (C.c_int, [_PTR]),
 }
 
 
@@ -296,6 +298,23 @@ class AugmentViewsCall(C.Structure):
                 ("rows", C.c_void_p), ("grid_ys", C.c_void_p), ("grid_xs", C.c_void_p), ("noise", C.c_void_p), ("drop_u", C.c_void_p),
                 ("seed", C.c_uint64), ("mean", C.c_float * 3), ("std", C.c_float * 3), ("out", C.c_void_p), ("out_mask", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+TTA_MAX_SCALES = 8                      # UAPS_TTA_MAX_SCALES
+
+
+class TTAViewsCall(C.Structure):
+    """uaps_tta_views_call (include/uaps_hip.h): every operand of uaps_tta_views, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("Cin", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("h", C.c_int32),
+                ("w", C.c_int32), ("flip", C.c_int32), ("x", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class TTAFoldCall(C.Structure):
+    """uaps_tta_fold_call (include/uaps_hip.h): every operand of uaps_tta_fold, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("S", C.c_int32), ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("flip", C.c_int32), ("logits", C.c_void_p * TTA_MAX_SCALES), ("h", C.c_int32 * TTA_MAX_SCALES),
+                ("w", C.c_int32 * TTA_MAX_SCALES), ("probs_sum", C.c_void_p), ("mask", C.c_void_p), ("conf", C.c_void_p),
+                ("stream", C.c_void_p)]
 
 
 SEG_NTERMS, SEG_MAX_CLASSES = 6, 8      # UAPS_SEG_NTERMS, UAPS_MAX_CLASSES

@@ -27,7 +27,7 @@ def predict(model: torch.nn.Module, images: torch.Tensor) -> Tuple[torch.Tensor,
 def predict_main(model: torch.nn.Module, images: torch.Tensor) -> torch.Tensor:
     """Main-head arg-max mask with ONLY the encoder and the main decoder run (the paper's "main decoder only" inference row,
     fig_data/decoder-effect.jpg: its time does not depend on the number of auxiliary decoders); the same mask as predict()[0].
-    Models without a `forward_main` (the ResNet variant) run every head."""
+    Models without a `forward_main` run every head."""
     model.eval()
     fm = getattr(model, "forward_main", None)
     logits = fm(images) if fm is not None else predict(model, images)[1][0]
@@ -141,13 +141,18 @@ def predict_with_uncertainty(model: torch.nn.Module, images: torch.Tensor):
 
 
 @torch.no_grad()
-def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]]) -> Dict[str, float]:
+def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None) -> Dict[str, float]:
     """The score table of notebook cell 25: mIoU, mDice and pixel accuracy of the main head computed image by image
-    (utilities/metrics.py conventions) and averaged over the images, in percent."""
+    (utilities/metrics.py conventions) and averaged over the images, in percent.  tta=True, or a tuple of scales: the arg-max of the
+    multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main head's."""
     miou, mdice, acc = [], [], []
     for x, y in batches:
-        _, heads = predict(model, x)
-        cms = metrics.seg_confusion_per_image(heads[0], y).cpu().numpy()
+        if tta:
+            from .tta import DEFAULT_SCALES, predict_tta
+            scored = predict_tta(model, x, scales=DEFAULT_SCALES if tta is True else tuple(tta), want=("probs",)).probs
+        else:
+            scored = predict(model, x)[1][0]
+        cms = metrics.seg_confusion_per_image(scored, y).cpu().numpy()
         for cm in cms:
             m = metrics.metrics_from_confusion(cm)
             miou.append(m["miou"]); mdice.append(m["mdice"]); acc.append(m["acc"])

@@ -342,7 +342,7 @@ class ResUAPS(nn.Module):
         with fused.stat_groups(2):
             return self.forward(fused.cat_batches(x_a, x_b), _groups=2)
 
-    def forward(self, x, _groups: int = 1):
+    def _prepare(self, x):
         if x.shape[2] % 8 or x.shape[3] % 8:
             raise ValueError("ResUAPS: height and width must be multiples of 8")
         if x.is_cuda:
@@ -353,6 +353,20 @@ class ResUAPS(nn.Module):
                 if getattr(self, "_bns", None) is None:
                     self._bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
                 bounds.refresh(self._bns)
+
+    def forward_main(self, x):
+        """Main-head logits only, as UNet_UAPS.forward_main: the encoder and the main decoder on clean features; no fan-out, no
+        auxiliary decoder.  The same tensor as forward(x)[0]."""
+        self._prepare(x)
+        return self.main_decoder(list(self.encoder.base_forward(x)))
+
+    def forward(self, x, _groups: int = 1, *, tta: bool = False):
+        """tta=True: the reference's `BaseNet.forward(x, tta=True)` surface (utilities/base.py:24-46) -- the summed multi-scale + flip
+        probability maps of the main head, [B, class_num, H, W] (tta.predict_tta: eval mode, no_grad)."""
+        if tta:
+            from .tta import predict_tta
+            return predict_tta(self, x, want=("probs",)).probs
+        self._prepare(x)
         feats = self.encoder.base_forward(x)
         kinds = [_PERTURBATIONS[i % 3] for i in range(self.n_aux)]
         if x.is_cuda and self.n_aux > 0:

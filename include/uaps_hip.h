@@ -1185,6 +1185,81 @@ typedef struct uaps_tta_fold_call {
 } uaps_tta_fold_call;
 int uaps_tta_fold(const uaps_tta_fold_call* call);
 
+/* ---------------------------------------------------------------------------------------------
+ * Defect instances and run-length masks: csrc/instances.hip.
+ *
+ * uaps_label_instances: connected components of a class mask.  mask int64 [B, H, W], any H, W >= 1.  A component is a maximal set of
+ *   pixels of one class, different from `background` when has_background == 1 (0: every class forms components), connected under
+ *   `connectivity` 4 or 8; touching regions of different classes are different components.  Components with fewer than min_area pixels
+ *   are removed.  Within an image the others are numbered 1 .. N_b by the raster index of their first pixel, ascending.
+ *     labels int32 [B, H, W]   the number of the pixel's component, 0 for background and removed components; always complete
+ *     count  int32 [B]         N_b, whatever max_instances is
+ *     table  int64 [B, max_instances, 9]   row k - 1 of image b describes component k:
+ *                              class, area, y0, x0, y1, x1 (half-open box), first_pixel (y * W + x), sum0, sum1;
+ *                              rows from count[b] on are zero, components numbered above max_instances have no row
+ *     sum0 / sum1              over the component's pixels, of q(v) = (int64) rintf(clamp(v, -65536, 65536) * 16777216.0f), q(NaN) = 0,
+ *                              v from map0 / map1 (fp32 [B, H, W], either NULL: the column stays 0; map1 needs map0).  Integer sums:
+ *                              exact, and the same bits from run to run whatever order the adds arrive in.
+ *   Launches: tile-local union-find in LDS, seam merging with agent-scope atomics, flatten + area, a two-level raster-order scan
+ *   over the surviving roots, the final pass.  No workgroup waits for another inside a launch.  The call does not synchronise.
+ *   workspace: uaps_instances_workspace_bytes(B, H, W) bytes, 256-byte aligned, the call's alone until it has run.
+ * Errors (nothing launched): UAPS_EINVAL null struct or mask / labels / count / table / workspace, non-positive dimension,
+ *   connectivity outside {4, 8}, min_area < 1, max_instances < 1, has_background outside {0, 1}, map1 without map0, struct_size
+ *   below this version's; UAPS_ERANGE H * W >= 2^31, B * H * W * 8 >= 2 GiB, table >= 2 GiB (by dimensions); UAPS_EWORKSPACE.
+ *
+ * uaps_rle_count / uaps_rle_encode / uaps_rle_decode: the reference's run-length exchange format (utilities/utilities.py:36-63,
+ *   mask2rle / make_mask).  The binary plane [mask == classes[c]] of image b is walked in column-major order; a run is a pair
+ *   (start, length) with a 1-based start.  Segment j = b * n_classes + c.
+ *   uaps_rle_count    mask int64 [B, H, W] -> col_offsets int32 [B * n_classes * W + 1]: the exclusive prefix sums of the number of
+ *                     runs that start in column x of segment j, at [j * W + x]; the last word is the total.  So the CSR offsets of the
+ *                     segments are col_offsets[j * W], j = 0 .. B * n_classes.
+ *   uaps_rle_encode   mask and the col_offsets of uaps_rle_count -> pairs int32 [total, 2].
+ *   uaps_rle_decode   pairs int32 [n_runs, 2], offsets int32 [B * n_classes + 1] (device) -> out [B, H, W], int64 or (out_uint8 == 1)
+ *                     uint8: zero, then pixels [start - 1, start - 1 + length) of the column-major walk receive classes[c]; later
+ *                     classes win where runs overlap (one launch per class, in order).  Runs need not be sorted; what leaves the
+ *                     plane is not written.
+ * Errors (nothing launched): UAPS_EINVAL null struct or a pointer the call uses, non-positive dimension, negative n_runs, out_uint8
+ *   outside {0, 1}, struct_size below this version's; UAPS_ERANGE n_classes outside [1, UAPS_RLE_MAX_CLASSES], H * W >= 2^31, a
+ *   tensor of 2 GiB or more (by dimensions), a class outside [0, 255] with out_uint8.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct uaps_instances_call {
+    uint32_t struct_size;
+    int32_t B, H, W;
+    int32_t connectivity;                        /* 4 or 8 */
+    int32_t has_background;                      /* 1: pixels of class `background` form no component */
+    int64_t background;
+    int32_t min_area, max_instances;
+    const int64_t* mask;                         /* [B][H][W] */
+    const float* map0;                           /* [B][H][W] or NULL */
+    const float* map1;                           /* [B][H][W] or NULL */
+    int32_t* labels;                             /* [B][H][W] */
+    int32_t* count;                              /* [B] */
+    int64_t* table;                              /* [B][max_instances][9] */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_instances_call;
+int uaps_instances_workspace_bytes(int B, int H, int W, size_t* bytes);
+int uaps_label_instances(const uaps_instances_call* call);
+
+#define UAPS_RLE_MAX_CLASSES 8
+typedef struct uaps_rle_call {
+    uint32_t struct_size;
+    int32_t B, H, W, n_classes;
+    int64_t classes[UAPS_RLE_MAX_CLASSES];
+    const int64_t* mask;                         /* count, encode: [B][H][W] */
+    int32_t* col_offsets;                        /* count writes, encode reads: [B * n_classes * W + 1] */
+    int32_t* pairs;                              /* encode writes, decode reads: [runs][2] */
+    const int32_t* offsets;                      /* decode: [B * n_classes + 1] */
+    int64_t n_runs;                              /* decode: rows of pairs */
+    void* out;                                   /* decode: [B][H][W] int64, or uint8 with out_uint8 == 1 */
+    int32_t out_uint8;
+    uaps_stream_t stream;
+} uaps_rle_call;
+int uaps_rle_count(const uaps_rle_call* call);
+int uaps_rle_encode(const uaps_rle_call* call);
+int uaps_rle_decode(const uaps_rle_call* call);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,9 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   predict_tta, tta_views, tta_fold, scaled_sizes, TTAResult, DEFAULT_SCALES   multi-scale + flip test-time augmentation
                                                     (utilities/base.py:24-46, BaseNet.forward(x, tta=True)); ResUAPS.forward(x, tta=True),
                                                     inference.evaluate(..., tta=True)
+  label_instances, InstanceResult, mask_to_rle, rle_to_mask, format_rle, parse_rle, rle_from_strings, RLE
+                                                    defect instances (connected components + per-defect table) and the reference's
+                                                    run-length masks (utilities/utilities.py:36-63); inference.predict_instances
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -48,6 +51,8 @@ from .pipelines import Recipe, Stage, RECIPES, ViewDraws, draw, augment_views, A
 from . import pipelines
 from .tta import predict_tta, tta_views, tta_fold, scaled_sizes, TTAResult, DEFAULT_SCALES
 from . import tta
+from .instances import label_instances, InstanceResult, mask_to_rle, rle_to_mask, format_rle, parse_rle, rle_from_strings, RLE
+from . import instances
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -159,6 +159,11 @@ SIGNATURES = {
     "uaps_bin_confusion": (C.c_int, [_PTR, _PTR] + [C.c_int] * 3 + [C.c_double, _PTR, _PTR]),
     "uaps_tta_views": (C.c_int, [_PTR]),
     "uaps_tta_fold": (C.c_int, [_PTR]),
+    "uaps_instances_workspace_bytes": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_size_t)]),
+    "uaps_label_instances": (C.c_int, [_PTR]),
+    "uaps_rle_count": (C.c_int, [_PTR]),
+    "uaps_rle_encode": (C.c_int, [_PTR]),
+    "uaps_rle_decode": (C.c_int, [_PTR]),
 }
 
 
@@ -315,6 +320,24 @@ class TTAFoldCall(C.Structure):
                 ("flip", C.c_int32), ("logits", C.c_void_p * TTA_MAX_SCALES), ("h", C.c_int32 * TTA_MAX_SCALES),
                 ("w", C.c_int32 * TTA_MAX_SCALES), ("probs_sum", C.c_void_p), ("mask", C.c_void_p), ("conf", C.c_void_p),
                 ("stream", C.c_void_p)]
+
+
+class InstancesCall(C.Structure):
+    """uaps_instances_call (include/uaps_hip.h): every operand of uaps_label_instances, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("connectivity", C.c_int32),
+                ("has_background", C.c_int32), ("background", C.c_int64), ("min_area", C.c_int32), ("max_instances", C.c_int32),
+                ("mask", C.c_void_p), ("map0", C.c_void_p), ("map1", C.c_void_p), ("labels", C.c_void_p), ("count", C.c_void_p),
+                ("table", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+RLE_MAX_CLASSES = 8                     # UAPS_RLE_MAX_CLASSES
+
+
+class RleCall(C.Structure):
+    """uaps_rle_call (include/uaps_hip.h): the operands of uaps_rle_count / _encode / _decode, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_classes", C.c_int32),
+                ("classes", C.c_int64 * RLE_MAX_CLASSES), ("mask", C.c_void_p), ("col_offsets", C.c_void_p), ("pairs", C.c_void_p),
+                ("offsets", C.c_void_p), ("n_runs", C.c_int64), ("out", C.c_void_p), ("out_uint8", C.c_int32), ("stream", C.c_void_p)]
 
 
 SEG_NTERMS, SEG_MAX_CLASSES = 6, 8      # UAPS_SEG_NTERMS, UAPS_MAX_CLASSES

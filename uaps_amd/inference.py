@@ -160,6 +160,25 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
             "images": len(acc)}
 
 
+@torch.no_grad()
+def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, min_area: int = 1, connectivity: int = 8,
+                      max_instances: int = 256):
+    """Defects instead of pixels: instances.label_instances on the main head's arg-max mask, with maps = (confidence, uncertainty).
+    The confidence is the main head's largest softmax; with tta (True, or a tuple of scales) mask and confidence are those of
+    tta.predict_tta.  The uncertainty is consistency.uncertainty_map(main, aux1) of the plain forward where the model has an auxiliary
+    head; a one-head model gets the confidence alone.  Returns an instances.InstanceResult (records() lists the defects)."""
+    from . import instances
+    mask, heads = predict(model, images)
+    if tta:
+        from .tta import DEFAULT_SCALES, predict_tta
+        r = predict_tta(model, images, scales=DEFAULT_SCALES if tta is True else tuple(tta), want=("mask", "conf"))
+        mask, conf = r.mask, r.conf
+    else:
+        conf = torch.softmax(heads[0], dim=1).amax(dim=1)
+    maps = (conf,) if len(heads) < 2 else (conf, consistency.uncertainty_map(heads[0], heads[1]))
+    return instances.label_instances(mask, maps, connectivity=connectivity, min_area=min_area, max_instances=max_instances)
+
+
 def load_for_inference(model: torch.nn.Module, checkpoint_path: str, device: Optional[torch.device] = None) -> Dict:
     """Notebook cell 4: `checkpoint = torch.load(path); model.load_state_dict(checkpoint['state_dict'])` -- accepts the
     `module.`-prefixed keys of the reference's nn.DataParallel checkpoints (UAPS_train.py:443-450) and plain ones."""

@@ -1260,6 +1260,77 @@ int uaps_rle_count(const uaps_rle_call* call);
 int uaps_rle_encode(const uaps_rle_call* call);
 int uaps_rle_decode(const uaps_rle_call* call);
 
+/* ---------------------------------------------------------------------------------------------
+ * Tiled (sliding-window) full-resolution inference: csrc/tiled.hip.  An image of any size is cut into overlapping tiles of the size
+ * the network runs at, the network runs on the tiles, and the tiles' probability maps are blended under a separable window.
+ *
+ * Geometry, per axis, with image extent n, tile extent t >= 1, overlap o, 0 <= o <= t / 2 (integer division), stride s = t - o:
+ *   n <= t   one tile at origin 0; its positions i >= n are mirror padding without repeating the edge: the source of position i is
+ *            m(i, n) = 0 when n == 1, else j = i mod 2 (n - 1), m = j when j < n, else 2 (n - 1) - j (any amount of padding).
+ *   n >  t   origins 0, s, 2 s, ... while < n - t, then a last origin n - t: the last tile is clamped into the image and overlaps its
+ *            neighbour by more.  No tile leaves the image, nothing is padded.
+ *   With o <= t / 2 a pixel lies in at most 3 tiles per axis (two regular ones and the clamped one), 9 in all.
+ *   Tiles are numbered g = b * T + iy * nx + ix, image-major, T = ny * nx.
+ * uaps_tile_origins (host only, launches nothing): *count = the number of tiles of one axis; origins, when not NULL, receives the first
+ *   min(*count, cap) origins in ascending order.  UAPS_EINVAL count == NULL, n < 1, tile < 1, overlap < 0, cap < 0; UAPS_ERANGE
+ *   overlap > tile / 2.
+ *
+ * uaps_tile_cut: x [B, Cin, H, W] -> out [g1 - g0, Cin, th, tw], the tiles g0 <= g < g1 of the numbering above; a pure copy (with the
+ *   mirrored index where an extent is below the tile's), bit-exact.  One launch per chunk of tiles: the caller bounds the forward's batch.
+ * uaps_tile_fold: the output side in one launch, gather form.  The tiles' logits [., C, th, tw] are read where the forwards left them:
+ *   logits[k] is the base of chunk k, which holds tiles [k * tiles_per_chunk, min((k + 1) * tiles_per_chunk, B * T)); n_chunks is
+ *   ceil(B * T / tiles_per_chunk) exactly.  A lane owns an output pixel (or four consecutive ones), finds the covering tiles from the
+ *   origin formula, and visits them in ascending (iy, ix) order: softmax over the C logits at the pixel, times wy[r] * wx[c] (r, c =
+ *   the pixel's position in the tile), added to C register accumulators and to the weight sum; at the end everything is divided by the
+ *   weight sum.  Written, whichever are not NULL:
+ *     probs [B, C, H, W] the weighted mean of the tiles' softmax (sums to 1);  mask [B, H, W] int64 its arg-max, the lowest index among
+ *     equal values;  conf [B, H, W] its largest value.
+ *   maps[m][k] (m < n_maps <= UAPS_TILE_MAX_MAPS): chunk k of a per-tile scalar map [., th, tw], blended by the same weights into
+ *     map_out[m] [B, H, W].  C == 0 with probs, mask and conf NULL and n_maps >= 1 blends maps alone.
+ *   wy [th], wx [tw]: fp32, device memory, every entry finite and > 0.  Other values give undefined values in the outputs, never an
+ *   access out of bounds.  Mirror padding of a tile is never read.  No LDS, no atomics, a fixed order: two runs give the same bits, and
+ *   so do two chunkings of the same tiles.  With W % 4 == 0 and 16-byte aligned outputs a lane owns four consecutive pixels and stores
+ *   16 bytes; otherwise one pixel -- the same arithmetic per pixel either way.
+ * Both structs are size-versioned like the test-time augmentation's.  The calls do not synchronise.
+ * Errors (nothing launched): UAPS_EINVAL null struct, struct_size below this version's, x / out / wy / wx NULL, no output at all, a
+ *   logits (C > 0) or maps chunk pointer or a map_out NULL below its count, non-positive dimension, negative overlap / C / n_maps,
+ *   C == 0 with probs, mask or conf, C > 0 with none of them, n_chunks != ceil(B * T / tiles_per_chunk), g0 / g1 outside 0 <= g0 < g1 <= B * T;
+ *   UAPS_ERANGE overlap > tile / 2, C == 1 (one-channel sigmoid heads have no form here) or C > UAPS_MAX_CLASSES, n_chunks >
+ *   UAPS_TILE_MAX_CHUNKS, n_maps > UAPS_TILE_MAX_MAPS, a tensor of 2 GiB or more (by dimensions; of the outputs only those that are
+ *   not NULL count).
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_TILE_MAX_CHUNKS 32
+#define UAPS_TILE_MAX_MAPS 2
+int uaps_tile_origins(int n, int tile, int overlap, int* count, int* origins, int cap);
+
+typedef struct uaps_tile_cut_call {
+    uint32_t struct_size;
+    int32_t B, Cin, H, W;
+    int32_t th, tw, oy, ox;                      /* tile extents and overlaps along y and x */
+    int32_t g0, g1;                              /* the tiles this launch writes */
+    const float* x;                              /* [B][Cin][H][W] */
+    float* out;                                  /* [g1 - g0][Cin][th][tw] */
+    uaps_stream_t stream;
+} uaps_tile_cut_call;
+int uaps_tile_cut(const uaps_tile_cut_call* call);
+
+typedef struct uaps_tile_fold_call {
+    uint32_t struct_size;
+    int32_t B, C, H, W;
+    int32_t th, tw, oy, ox;
+    int32_t n_chunks, tiles_per_chunk, n_maps;
+    const float* logits[UAPS_TILE_MAX_CHUNKS];   /* device, chunk k: [tiles of the chunk][C][th][tw] */
+    const float* maps[UAPS_TILE_MAX_MAPS][UAPS_TILE_MAX_CHUNKS];    /* device, chunk k of map m: [tiles of the chunk][th][tw] */
+    const float* wy;                             /* [th] */
+    const float* wx;                             /* [tw] */
+    float* probs;                                /* [B][C][H][W] or NULL */
+    int64_t* mask;                               /* [B][H][W] or NULL */
+    float* conf;                                 /* [B][H][W] or NULL */
+    float* map_out[UAPS_TILE_MAX_MAPS];          /* [B][H][W] each */
+    uaps_stream_t stream;
+} uaps_tile_fold_call;
+int uaps_tile_fold(const uaps_tile_fold_call* call);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,9 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   label_instances, InstanceResult, mask_to_rle, rle_to_mask, format_rle, parse_rle, rle_from_strings, RLE
                                                     defect instances (connected components + per-defect table) and the reference's
                                                     run-length masks (utilities/utilities.py:36-63); inference.predict_instances
+  predict_tiled, tile_plan, tile_window, tile_cut, tile_fold, TilePlan, TiledResult   sliding-window inference at full resolution:
+                                                    overlapping tiles blended under a window; inference.evaluate(..., tiled=True),
+                                                    inference.predict_instances(..., tiled=True)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -53,6 +56,8 @@ from .tta import predict_tta, tta_views, tta_fold, scaled_sizes, TTAResult, DEFA
 from . import tta
 from .instances import label_instances, InstanceResult, mask_to_rle, rle_to_mask, format_rle, parse_rle, rle_from_strings, RLE
 from . import instances
+from .tiled import predict_tiled, tile_plan, tile_window, tile_cut, tile_fold, TilePlan, TiledResult
+from . import tiled
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -164,6 +164,9 @@ SIGNATURES = {
     "uaps_rle_count": (C.c_int, [_PTR]),
     "uaps_rle_encode": (C.c_int, [_PTR]),
     "uaps_rle_decode": (C.c_int, [_PTR]),
+    "uaps_tile_origins": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "uaps_tile_cut": (C.c_int, [_PTR]),
+    "uaps_tile_fold": (C.c_int, [_PTR]),
 }
 
 
@@ -338,6 +341,25 @@ class RleCall(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_classes", C.c_int32),
                 ("classes", C.c_int64 * RLE_MAX_CLASSES), ("mask", C.c_void_p), ("col_offsets", C.c_void_p), ("pairs", C.c_void_p),
                 ("offsets", C.c_void_p), ("n_runs", C.c_int64), ("out", C.c_void_p), ("out_uint8", C.c_int32), ("stream", C.c_void_p)]
+
+
+TILE_MAX_CHUNKS, TILE_MAX_MAPS = 32, 2  # UAPS_TILE_MAX_CHUNKS, UAPS_TILE_MAX_MAPS
+
+
+class TileCutCall(C.Structure):
+    """uaps_tile_cut_call (include/uaps_hip.h): every operand of uaps_tile_cut, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("Cin", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("th", C.c_int32),
+                ("tw", C.c_int32), ("oy", C.c_int32), ("ox", C.c_int32), ("g0", C.c_int32), ("g1", C.c_int32), ("x", C.c_void_p),
+                ("out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class TileFoldCall(C.Structure):
+    """uaps_tile_fold_call (include/uaps_hip.h): every operand of uaps_tile_fold, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("th", C.c_int32),
+                ("tw", C.c_int32), ("oy", C.c_int32), ("ox", C.c_int32), ("n_chunks", C.c_int32), ("tiles_per_chunk", C.c_int32),
+                ("n_maps", C.c_int32), ("logits", C.c_void_p * TILE_MAX_CHUNKS), ("maps", (C.c_void_p * TILE_MAX_CHUNKS) * TILE_MAX_MAPS),
+                ("wy", C.c_void_p), ("wx", C.c_void_p), ("probs", C.c_void_p), ("mask", C.c_void_p), ("conf", C.c_void_p),
+                ("map_out", C.c_void_p * TILE_MAX_MAPS), ("stream", C.c_void_p)]
 
 
 SEG_NTERMS, SEG_MAX_CLASSES = 6, 8      # UAPS_SEG_NTERMS, UAPS_MAX_CLASSES

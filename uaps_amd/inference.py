@@ -140,14 +140,30 @@ def predict_with_uncertainty(model: torch.nn.Module, images: torch.Tensor):
     return mask, var1, 1.0 - var1
 
 
+def _tiled_kwargs(tiled, tta, what):
+    """The predict_tiled keywords of a `tiled` argument (True: the defaults); tiled together with tta has no form."""
+    if tta:
+        raise ValueError(f"{what}: tiled together with tta is not built (TTA inside tiles is out of scope)")
+    if tiled is True:
+        return {}
+    if not isinstance(tiled, dict):
+        raise TypeError(f"{what}: tiled is True or a dict of predict_tiled keywords")
+    return dict(tiled)
+
+
 @torch.no_grad()
-def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None) -> Dict[str, float]:
+def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None, tiled=None) -> Dict[str, float]:
     """The score table of notebook cell 25: mIoU, mDice and pixel accuracy of the main head computed image by image
     (utilities/metrics.py conventions) and averaged over the images, in percent.  tta=True, or a tuple of scales: the arg-max of the
-    multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main head's."""
+    multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main head's.  tiled=True, or a dict of
+    tiled.predict_tiled keywords: images of any size are scored on the blended probability maps of sliding-window inference."""
     miou, mdice, acc = [], [], []
+    tiled_kw = _tiled_kwargs(tiled, tta, "evaluate") if tiled else None
     for x, y in batches:
-        if tta:
+        if tiled_kw is not None:
+            from .tiled import predict_tiled
+            scored = predict_tiled(model, x, **{**tiled_kw, "want": ("probs",)}).probs
+        elif tta:
             from .tta import DEFAULT_SCALES, predict_tta
             scored = predict_tta(model, x, scales=DEFAULT_SCALES if tta is True else tuple(tta), want=("probs",)).probs
         else:
@@ -161,13 +177,22 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
 
 
 @torch.no_grad()
-def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, min_area: int = 1, connectivity: int = 8,
+def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, tiled=None, min_area: int = 1, connectivity: int = 8,
                       max_instances: int = 256):
     """Defects instead of pixels: instances.label_instances on the main head's arg-max mask, with maps = (confidence, uncertainty).
     The confidence is the main head's largest softmax; with tta (True, or a tuple of scales) mask and confidence are those of
     tta.predict_tta.  The uncertainty is consistency.uncertainty_map(main, aux1) of the plain forward where the model has an auxiliary
-    head; a one-head model gets the confidence alone.  Returns an instances.InstanceResult (records() lists the defects)."""
+    head; a one-head model gets the confidence alone.  tiled (True, or a dict of tiled.predict_tiled keywords): mask, confidence and
+    the blended per-tile uncertainty of sliding-window inference, for images of any size.  Returns an instances.InstanceResult
+    (records() lists the defects)."""
     from . import instances
+    if tiled:
+        from .tiled import predict_tiled
+        kw = {**_tiled_kwargs(tiled, tta, "predict_instances"), "want": ("mask", "conf")}
+        kw.setdefault("uncertainty", "auto")
+        r = predict_tiled(model, images, **kw)
+        return instances.label_instances(r.mask, (r.conf,) + tuple(r.maps), connectivity=connectivity, min_area=min_area,
+                                         max_instances=max_instances)
     mask, heads = predict(model, images)
     if tta:
         from .tta import DEFAULT_SCALES, predict_tta

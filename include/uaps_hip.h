@@ -1331,6 +1331,78 @@ typedef struct uaps_tile_fold_call {
 } uaps_tile_fold_call;
 int uaps_tile_fold(const uaps_tile_fold_call* call);
 
+/* ---------------------------------------------------------------------------------------------
+ * Boundary metrics: csrc/surface.hip.  An exact squared Euclidean distance transform (separable, integers only) and, on top of it,
+ * the directed surface distances between two label maps reduced to one int64 row per (image, class).  2-D maps, isotropic pixels,
+ * 1 <= H, W <= UAPS_SURFACE_MAX_EXTENT.  Every quantity is an integer: results are exact and the same bits from run to run.
+ *
+ * Labels travel as `*_dtype` = UAPS_LABEL_U8 / _I32 / _I64 (the element type of the array behind the pointer).
+ *
+ * uaps_edt_sq: out int32 [B, H, W] = the squared distance of every pixel to the nearest pixel whose mask value is 0 (0 at such
+ *   pixels; scipy.ndimage.distance_transform_edt(mask) squared); UAPS_EDT_NO_FEATURE everywhere in an image without a zero pixel.
+ *   Two launches: a column sweep (one lane per column, down and up) that writes the distance along the column as uint16, and a row
+ *   pass that stages one row of its squares in LDS, where every lane scans outwards from its pixel until dx^2 reaches its best value.
+ *   workspace: uaps_edt_workspace_bytes(B, H, W) bytes, 256-byte aligned, the call's alone until it has run.
+ *
+ * uaps_surface_distances: pred and target are label maps [B, H, W]; a value outside [0, C) belongs to no class.  With pred_scores
+ *   (fp32 [B, C, H, W]) instead of pred, the prediction is its arg-max over the classes, the lowest index among equal scores.
+ *   The surface of class c in a map m: m == c and one of the four neighbours is != c or outside the image.  For every surface pixel
+ *   of the prediction d2_pg = the smallest dy^2 + dx^2 to a surface pixel of the target, d2_gp likewise the other way round.
+ *     table int64 [B, C, UAPS_SURFACE_COLUMNS]: n_pred, n_gt, max_pg, max_gp, sum16_pg, sum16_gp, within_pg, within_gp, rank_lo,
+ *       rank_hi, q_lo, q_hi.  sum16 = sum of floor(2^16 sqrt(d2)) (the integer square root of d2 << 32); within = the number of
+ *       surface pixels with d2 <= tol_d2 (0 with has_tolerance == 0); with N = n_pred + n_gt and h = (double)(N - 1) * percentile_frac,
+ *       rank_lo = floor(h), rank_hi = min(rank_lo + 1, N - 1), and q_lo / q_hi the squared distances of those ranks among the N
+ *       pooled values in ascending order.  A pair with n_pred == 0 or n_gt == 0 has zeros in every column after n_gt.
+ *   Launches: [arg-max,] the column sweep for both sides and all classes from one read of each label map (surface membership is
+ *   decided on the fly, no surface mask is written), the row pass (only lanes on a surface pixel scan; counts, maxima and sums go
+ *   through a workgroup reduction and 64-bit integer atomics), the ranks, then three histogram passes (9 + 8 + 8 bits, LDS histograms
+ *   flushed with integer atomics, many workgroups per plane) each followed by the choice of the bin.  No float atomics; the call does
+ *   not synchronise.
+ *   workspace: uaps_surface_workspace_bytes(B, C, H, W) bytes, 256-byte aligned, the call's alone until it has run.
+ * Both structs are size-versioned (fields are only ever appended; a larger struct_size is accepted and what it appends is not read).
+ * Errors (nothing launched): UAPS_EINVAL null struct or a pointer the call uses, both or neither of pred / pred_scores, non-positive
+ *   dimension, unknown dtype, percentile_frac outside [0, 1], has_tolerance outside {0, 1}, negative tol_d2, struct_size below this
+ *   version's; UAPS_ERANGE H or W above UAPS_SURFACE_MAX_EXTENT, C outside [1, UAPS_MAX_CLASSES], a tensor or the workspace of 2 GiB
+ *   or more (by dimensions); UAPS_EWORKSPACE.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_SURFACE_MAX_EXTENT 4096
+#define UAPS_SURFACE_COLUMNS 12
+#define UAPS_EDT_NO_FEATURE 1073741824           /* 2^30 */
+#define UAPS_LABEL_U8 1
+#define UAPS_LABEL_I32 4
+#define UAPS_LABEL_I64 8
+
+typedef struct uaps_edt_call {
+    uint32_t struct_size;
+    int32_t B, H, W;
+    int32_t mask_dtype;                          /* UAPS_LABEL_* */
+    const void* mask;                            /* [B][H][W] */
+    int32_t* out;                                /* [B][H][W] */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_edt_call;
+int uaps_edt_workspace_bytes(int B, int H, int W, size_t* bytes);
+int uaps_edt_sq(const uaps_edt_call* call);
+
+typedef struct uaps_surface_call {
+    uint32_t struct_size;
+    int32_t B, C, H, W;
+    int32_t pred_dtype, target_dtype;            /* UAPS_LABEL_*; pred_dtype is not read with pred_scores */
+    const void* pred;                            /* [B][H][W] or NULL */
+    const float* pred_scores;                    /* [B][C][H][W] or NULL: exactly one of the two */
+    const void* target;                          /* [B][H][W] */
+    double percentile_frac;                      /* percentile / 100.0, in [0, 1] */
+    int32_t has_tolerance;
+    int64_t tol_d2;                              /* floor(tolerance^2) */
+    int64_t* table;                              /* [B][C][UAPS_SURFACE_COLUMNS] */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_surface_call;
+int uaps_surface_workspace_bytes(int B, int C, int H, int W, size_t* bytes);
+int uaps_surface_distances(const uaps_surface_call* call);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,8 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   predict_tiled, tile_plan, tile_window, tile_cut, tile_fold, TilePlan, TiledResult   sliding-window inference at full resolution:
                                                     overlapping tiles blended under a window; inference.evaluate(..., tiled=True),
                                                     inference.predict_instances(..., tiled=True)
+  surface_distances, distance_transform_sq, SurfaceResult, SURFACE_COLUMNS   boundary metrics on an exact device distance transform:
+                                                    HD, HD95, ASSD, NSD under medpy's conventions; inference.evaluate(..., surface=True)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -58,6 +60,8 @@ from .instances import label_instances, InstanceResult, mask_to_rle, rle_to_mask
 from . import instances
 from .tiled import predict_tiled, tile_plan, tile_window, tile_cut, tile_fold, TilePlan, TiledResult
 from . import tiled
+from .surface import surface_distances, distance_transform_sq, SurfaceResult, SURFACE_COLUMNS
+from . import surface
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -167,6 +167,10 @@ SIGNATURES = {
     "uaps_tile_origins": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     "uaps_tile_cut": (C.c_int, [_PTR]),
     "uaps_tile_fold": (C.c_int, [_PTR]),
+    "uaps_edt_workspace_bytes": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_size_t)]),
+    "uaps_edt_sq": (C.c_int, [_PTR]),
+    "uaps_surface_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
+    "uaps_surface_distances": (C.c_int, [_PTR]),
 }
 
 
@@ -360,6 +364,21 @@ class TileFoldCall(C.Structure):
                 ("n_maps", C.c_int32), ("logits", C.c_void_p * TILE_MAX_CHUNKS), ("maps", (C.c_void_p * TILE_MAX_CHUNKS) * TILE_MAX_MAPS),
                 ("wy", C.c_void_p), ("wx", C.c_void_p), ("probs", C.c_void_p), ("mask", C.c_void_p), ("conf", C.c_void_p),
                 ("map_out", C.c_void_p * TILE_MAX_MAPS), ("stream", C.c_void_p)]
+
+
+class EdtCall(C.Structure):
+    """uaps_edt_call (include/uaps_hip.h): every operand of uaps_edt_sq, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("mask_dtype", C.c_int32),
+                ("mask", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
+class SurfaceCall(C.Structure):
+    """uaps_surface_call (include/uaps_hip.h): every operand of uaps_surface_distances, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("pred_dtype", C.c_int32), ("target_dtype", C.c_int32), ("pred", C.c_void_p), ("pred_scores", C.c_void_p),
+                ("target", C.c_void_p), ("percentile_frac", C.c_double), ("has_tolerance", C.c_int32), ("tol_d2", C.c_int64),
+                ("table", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
 SEG_NTERMS, SEG_MAX_CLASSES = 6, 8      # UAPS_SEG_NTERMS, UAPS_MAX_CLASSES

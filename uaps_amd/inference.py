@@ -151,14 +151,42 @@ def _tiled_kwargs(tiled, tta, what):
     return dict(tiled)
 
 
+def _surface_kwargs(surface):
+    """The keywords of a `surface` argument (True: the defaults)."""
+    if surface is True:
+        return {}
+    if not isinstance(surface, dict) or set(surface) - {"percentile", "tolerance", "classes"}:
+        raise TypeError("evaluate: surface is True or a dict with the keywords percentile, tolerance and classes")
+    return dict(surface)
+
+
+def _surface_sums(scored: torch.Tensor, y: torch.Tensor, kw) -> torch.Tensor:
+    """float64 [4] on the device: the sums of hd95, assd and nsd (0 without a tolerance) over the valid pairs of the chosen classes
+    (default 1 .. C-1) of one batch, and their number."""
+    from .surface import surface_distances
+    Cn = scored.shape[1]
+    r = surface_distances(scored.float(), y, Cn, percentile=kw.get("percentile", 95.0), tolerance=kw.get("tolerance"))
+    classes = list(range(1, Cn)) if kw.get("classes") is None else [int(c) for c in kw["classes"]]
+    ok = r.valid[:, classes]
+    total = lambda v: torch.where(ok, v[:, classes], torch.zeros_like(v[:, classes])).sum()
+    nsd = total(r.nsd) if r.tolerance is not None else torch.zeros((), dtype=torch.float64, device=ok.device)
+    return torch.stack([total(r.hd95), total(r.assd), nsd, ok.sum().to(torch.float64)])
+
+
 @torch.no_grad()
-def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None, tiled=None) -> Dict[str, float]:
+def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None, tiled=None,
+             surface=None) -> Dict[str, float]:
     """The score table of notebook cell 25: mIoU, mDice and pixel accuracy of the main head computed image by image
     (utilities/metrics.py conventions) and averaged over the images, in percent.  tta=True, or a tuple of scales: the arg-max of the
     multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main head's.  tiled=True, or a dict of
-    tiled.predict_tiled keywords: images of any size are scored on the blended probability maps of sliding-window inference."""
+    tiled.predict_tiled keywords: images of any size are scored on the blended probability maps of sliding-window inference.
+    surface=True, or a dict with the keywords percentile, tolerance and classes: the boundary metrics of surface.surface_distances
+    on the same scored maps are added -- "HD95(px)" and "ASSD(px)" (and "NSD(%)" with a tolerance), the means over the valid
+    (image, class) pairs of the whole run, and "surface_pairs", their number.  The pairs are summed on the device; one copy at the end."""
     miou, mdice, acc = [], [], []
     tiled_kw = _tiled_kwargs(tiled, tta, "evaluate") if tiled else None
+    surf_kw = _surface_kwargs(surface) if surface else None
+    surf_sums = []
     for x, y in batches:
         if tiled_kw is not None:
             from .tiled import predict_tiled
@@ -168,12 +196,23 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
             scored = predict_tta(model, x, scales=DEFAULT_SCALES if tta is True else tuple(tta), want=("probs",)).probs
         else:
             scored = predict(model, x)[1][0]
+        if surf_kw is not None:
+            surf_sums.append(_surface_sums(scored, y, surf_kw))
         cms = metrics.seg_confusion_per_image(scored, y).cpu().numpy()
         for cm in cms:
             m = metrics.metrics_from_confusion(cm)
             miou.append(m["miou"]); mdice.append(m["mdice"]); acc.append(m["acc"])
-    return {"mIoU(%)": float(np.mean(miou) * 100), "mDice(%)": float(np.mean(mdice) * 100), "Accuracy(%)": float(np.mean(acc) * 100),
-            "images": len(acc)}
+    out = {"mIoU(%)": float(np.mean(miou) * 100), "mDice(%)": float(np.mean(mdice) * 100), "Accuracy(%)": float(np.mean(acc) * 100),
+           "images": len(acc)}
+    if surf_kw is not None:
+        tot = torch.stack(surf_sums).sum(dim=0).cpu().tolist() if surf_sums else [0.0] * 4
+        pairs = int(tot[3])
+        mean = lambda v: v / pairs if pairs else float("nan")
+        out["HD95(px)"], out["ASSD(px)"] = mean(tot[0]), mean(tot[1])
+        if surf_kw.get("tolerance") is not None:
+            out["NSD(%)"] = mean(tot[2]) * 100
+        out["surface_pairs"] = pairs
+    return out
 
 
 @torch.no_grad()

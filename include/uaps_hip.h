@@ -963,6 +963,25 @@ int uaps_bn_act_bwd_finalize(const void* partials, int parts_per_image, const fl
                              float* dgamma, float* dbeta, float* dconv_bias, float* dy_bound, uaps_stream_t stream);
 int uaps_bn_act_bwd_apply(const float* dout, const float* y, const float* coef, float slope, int B, int C, int H, int W, int groups,
                           float* dy, uaps_stream_t stream);
+/* The backward of a decoder's class convolution and the reductions of the BatchNorm in front of it as ONE pass (csrc/head_bwd_row.hip)
+ * where uaps_conv_bwd_data, uaps_conv_bwd_weight_partial_bn and the sums pass of uaps_bn_act_bwd_prepare ran one after the other.
+ * dlogits [B,Cout,H,W] is the gradient of z = conv(leaky_relu(batch_norm_train(y)), w) with y [B,Cin,H,W] the raw output of the
+ * convolution in front and xf [groups][Cin] float2 (scale, shift) from uaps_bn_finalize_train; wb the packed input-gradient weights
+ * of w (uaps_conv_pack_weights).  Written: g [B,Cin,H,W] = d(activation), bit-identical to uaps_conv_bwd_data's; the per-split
+ * slabs of dw (and dbias with want_bias) in the workspace layout uaps_conv_wrw_workspace_bytes(B, Cin, Cout, H, W, ks, cfg) reports,
+ * for uaps_conv_bwd_weight_reduce[_batch]; partials float2 [Cin][B][H / 16] = (sum d, sum d x_hat) per 16-row run and maxes = two
+ * bounds (2 * UAPS_BOUND_FLOATS floats, zeroed by the caller with uaps_zero_bounds) raised to max|d| and max|x_hat|, for
+ * uaps_bn_act_bwd_finalize(partials, H / 16, maxes, ...).  dy_bound / x_bound (times their host factors) bound |dlogits| and the
+ * activation, as uaps_call_hints::bound[0 / 1] of the weight gradient.  Only enqueues on `stream`; no float atomics, two launches
+ * give the same bits.
+ * One form: ks == 3, Cin == 16, Cout <= 4, W == 256, H % 16 == 0, mode 2 (fp16-split arithmetic) with both bounds present, 16-byte
+ * aligned tensors, cfg without dilation / exact / split bits.  Anything else returns UAPS_ENOFORM with nothing launched: make the
+ * three separate calls. */
+int uaps_head_bwd_fused(const float* dlogits, const float* y, const void* xf, float slope, int groups, const float* wb,
+                        const float* dy_bound, float dy_mul, const float* x_bound, float x_mul, const float* save_mean,
+                        const float* save_invstd, const float* gamma, const float* beta, int want_bias, int B, int Cin, int Cout,
+                        int H, int W, int ks, int cfg, float* g, void* partials, float* maxes, void* workspace,
+                        size_t workspace_bytes, uaps_stream_t stream);
 
 /* The same when the join's output had k <= 4 consumers: dx = (dout[0] + ... + dout[k-1]) * (out > 0), the k gradients (host
  * array of device pointers) summed in order by this pass instead of by k - 1 accumulation passes in front of it. */

@@ -9,6 +9,7 @@ fallback on this path: CPU tensors are refused.
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -644,10 +645,18 @@ def conv_fwd_raw(x: torch.Tensor, wf: torch.Tensor, bias: Optional[torch.Tensor]
 _FUSED_BSUM = config.flag("UAPS_FUSED_BN_SUMS", False)
 
 
-def conv_bwd_data_raw(dy: torch.Tensor, wb: torch.Tensor, Cin: int, ks: int, cfg: int = 0, dyb=None, bsum=None):
+def conv_bwd_data_raw(dy: torch.Tensor, wb: torch.Tensor, Cin: int, ks: int, cfg: int = 0, dyb=None, bsum=None, head=None):
     """bsum = (y, mean, invstd, gamma, beta, slope, groups): dx is d(activation) of the train-mode BatchNorm + LeakyReLU whose raw
     input is y; where the layer's kernel can (uaps_call_hints::bsum_*), its epilogue also forms that BatchNorm's backward sums --
-    then (dx, partials, maxes) comes back for lazybn.prepare_from_partials, else (dx, None, None)."""
+    then (dx, partials, maxes) comes back for lazybn.prepare_from_partials, else (dx, None, None).
+    head = (xf, xb, want_bias, ws), with bsum: the caller also wants this convolution's weight gradient, whose input is
+    leaky_relu(fma(y, xf)) bounded by xb; where the one-pass kernel of out_conv's backward has the form (head_bwd_fused) it forms dx,
+    the sums and the weight-gradient slabs in `ws` together, and a fourth value says whether it did (True: follow with _wrw_reduce;
+    False: nothing of the weight gradient was computed)."""
+    if head is not None and bsum is not None and head_bwd_eligible(dy, bsum[0], ks):
+        res = head_bwd_fused(dy, dyb, bsum[0], head[0], head[1], wb, bsum[1], bsum[2], bsum[3], bsum[4], bsum[5], bsum[6], head[2], cfg, head[3])
+        if res is not None:
+            return res + (True,)
     B, Cout, H, W = dy.shape
     dev = dy.device
     dx = torch.empty((B, Cin, H, W), dtype=torch.float32, device=dev)
@@ -665,13 +674,55 @@ def conv_bwd_data_raw(dy: torch.Tensor, wb: torch.Tensor, Cin: int, ks: int, cfg
                 rc = L.uaps_conv_bwd_data_h(hh, dy.data_ptr(), wb.data_ptr(), dx.data_ptr(), B, Cin, Cout, H, W, ks, cfg, _lib.current_stream(dev))
         if rc != ENOFORM:
             _lib.check(rc, "uaps_conv_bwd_data")
-            return dx, partials, maxes
+            return (dx, partials, maxes) + ((False,) if head is not None else ())
         partials = maxes = None
     hh = _lib.mk_hints((dyb,)) if dyb is not None else None
     with _lib.device_guard(dev), _timed(BWD_DATA, B, Cin, Cout, H, W, ks, cfg, hh, x=dy, y=dx):
         rc = L.uaps_conv_bwd_data_h(hh, dy.data_ptr(), wb.data_ptr(), dx.data_ptr(), B, Cin, Cout, H, W, ks, cfg, _lib.current_stream(dev))
     _lib.check(rc, "uaps_conv_bwd_data")
+    if head is not None:
+        return dx, None, None, False
     return (dx, None, None) if bsum is not None else dx
+
+
+# out_conv's backward and the BatchNorm-backward sums of the layer in front as one full-width-row pass (csrc/head_bwd_row.hip)
+_FUSED_HEAD = config.flag("UAPS_FUSED_HEAD_BWD", True)
+HEAD_BWD_KERNEL = "head_bwd_row_kernel"
+
+
+def head_bwd_eligible(dz: torch.Tensor, y: torch.Tensor, ks: int) -> bool:
+    """May head_bwd_fused run for d logits `dz` and raw conv output `y` (the library checks the rest and answers ENOFORM)?"""
+    return (_FUSED_HEAD and ks == 3 and y.shape[1] == 16 and dz.shape[1] <= 4 and y.shape[3] == 256 and y.shape[2] % 16 == 0
+            and get_mode() == "h16")
+
+
+def head_bwd_fused(dz: torch.Tensor, dzb, y: torch.Tensor, xf: torch.Tensor, xb, wb: torch.Tensor, mean, invstd, gamma, beta,
+                   slope: float, groups: int, want_bias: bool, cfg: int, ws: torch.Tensor):
+    """uaps_head_bwd_fused: (g, partials, maxes) with the weight-gradient slabs written to `ws` (follow with _wrw_reduce and
+    lazybn.prepare_from_partials), or None -- nothing launched, nothing written -- where the call is outside the kernel's form."""
+    B, Cout, H, W = dz.shape
+    Cin = y.shape[1]
+    dev = y.device
+    g = torch.empty_like(y)
+    partials = torch.empty((Cin, B, max(H // 16, 1), 2), dtype=torch.float32, device=dev)
+    maxes = torch.empty(2 * bounds.FLOATS, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    on = KERNEL_EVENTS is not None and (EVENT_FILTER is None or HEAD_BWD_KERNEL in EVENT_FILTER)
+    with _lib.device_guard(dev):
+        st = _lib.current_stream(dev)
+        _lib.check(L.uaps_zero_bounds(maxes.data_ptr(), maxes.numel(), st), "uaps_zero_bounds")
+        with (_lib.LaunchTimer() if on else contextlib.nullcontext()) as timer:
+            rc = L.uaps_head_bwd_fused(dz.data_ptr(), y.data_ptr(), xf.data_ptr(), float(slope), int(groups), wb.data_ptr(),
+                                       dzb[0].data_ptr() if dzb is not None else None, float(dzb[1]) if dzb is not None else 1.0,
+                                       xb[0].data_ptr() if xb is not None else None, float(xb[1]) if xb is not None else 1.0,
+                                       mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), int(want_bias), B, Cin, Cout,
+                                       H, W, 3, cfg, g.data_ptr(), partials.data_ptr(), maxes.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        if on and rc == 0:                            # both contractions: the weight gradient and the input gradient
+            KERNEL_EVENTS.setdefault(HEAD_BWD_KERNEL, []).append((timer.start, timer.stop, 2 * 2.0 * B * H * W * Cin * Cout * 9))
+    if rc == ENOFORM:
+        return None
+    _lib.check(rc, "uaps_head_bwd_fused")
+    return g, partials, maxes
 
 
 def conv_bwd_weight_raw(dy: torch.Tensor, x: torch.Tensor, ks: int, want_bias: bool, cfg: int = 0, wkey=None, bkey=None,

@@ -350,7 +350,15 @@ class _BnActConv(torch.autograd.Function):
         lazy_up = ctx.lazy_up and not lazybn.observed(y)      # (a hook / retain_grad registered on y since the forward gets the true gradient)
         partials = maxes = None
         if lazy_up:      # where the input-gradient kernel can, its epilogue forms this BatchNorm's backward sums (no pass of their own)
-            da, partials, maxes = _conv.conv_bwd_data_raw(dz, wb, Cc, ks, cfg, dyb=dzb, bsum=(y, stats[0], stats[1], gamma, beta, slope, groups))
+            # out_conv at the 256-wide level: input gradient, this BatchNorm's backward sums AND the weight-gradient slabs from ONE pass
+            # over (d logits, y) (csrc/head_bwd_row.hip); res[3] False: outside that kernel's form, the weight gradient runs below
+            head = (xf, xb, want_db, cws) if (not done_w and ctx.needs_input_grad[12]) else None
+            res = _conv.conv_bwd_data_raw(dz, wb, Cc, ks, cfg, dyb=dzb, bsum=(y, stats[0], stats[1], gamma, beta, slope, groups), head=head)
+            da, partials, maxes = res[:3]
+            if head is not None and res[3]:
+                with _lib.device_guard(dev):
+                    _conv._wrw_reduce(cws, dw, db, B, Cc, Cout, H, W, ks, cfg, _lib.current_stream(dev), ctx.prefs, ctx.step)
+                done_w = True
         else:
             da = _conv.conv_bwd_data_raw(dz, wb, Cc, ks, cfg, dyb=dzb)
         if not done_w:

@@ -1422,6 +1422,60 @@ typedef struct uaps_surface_call {
 int uaps_surface_workspace_bytes(int B, int C, int H, int W, size_t* bytes);
 int uaps_surface_distances(const uaps_surface_call* call);
 
+/* ---------------------------------------------------------------------------------------------
+ * Defect matching against ground truth: csrc/match.hip.  Two results of uaps_label_instances over the same B, H, W -- the prediction's
+ * (labels, count, table with max_pred rows) and the ground truth's (max_gt rows) -- are matched defect by defect.  Integers throughout.
+ *
+ *   Pixel rule   a pixel of image b with p = pred_labels, g = target_labels counts iff 1 <= p <= max_pred, 1 <= g <= max_gt and the
+ *                class columns of the two table rows are equal (class_agnostic == 1: always); it adds 1 to inter[b, p, g].  Components
+ *                numbered above max_instances have no row and take part in nothing.
+ *   Match rule   with union = area_p + area_g - inter (areas from the tables), p and g are matched iff
+ *                (double) inter > iou_threshold * (double) union -- strict, the panoptic-quality rule; 0.5 <= iou_threshold < 1, where
+ *                a component has at most one match (2 inter > union >= area, so more than half of it lies in the partner).
+ *     pred_out   int64 [B, max_pred, 4]: partner (the target number with the largest intersection, the lowest on ties, 0: none), inter
+ *                (with that partner), covered (the sum of inter[b, p, :]), matched (0 / 1); rows from min(count, max_pred) on are zero
+ *     target_out int64 [B, max_gt, 4]: the same from the ground truth's side
+ *     counts     int64 [B, num_classes, 3]: tp, n_pred, n_gt per image and class, over the in-table components with a class in
+ *                [0, num_classes); tp is attributed to the ground-truth component's class
+ *   Launches: zero (the min(count_p, max_pred) x min(count_g, max_gt) corner of every image's pair matrix, from the device-side
+ *   counts, and `counts`), the pair count (both label tensors streamed once, four pixels a lane with 16-byte loads where H * W % 4 == 0
+ *   and the tensors are 16-byte aligned; one integer atomicAdd per run of equal (p, g) inside a wave, whole waves of one pair carried on in
+ *   registers and combined per workgroup in LDS), one reduction per side.  Integer atomics only, no workgroup waits for another: two
+ *   runs give the same bits.  The call does not synchronise.
+ *   workspace: uaps_match_workspace_bytes(B, max_pred, max_gt) bytes (the dense pair matrix int32 [B, max_pred, max_gt]), 256-byte
+ *   aligned, the call's alone until it has run.
+ * The struct is size-versioned (fields are only ever appended; a larger struct_size is accepted and what it appends is not read).
+ * Errors (nothing launched): UAPS_EINVAL null struct or pointer, non-positive dimension or max_pred / max_gt, struct_size below this
+ *   version's, class_agnostic outside {0, 1}, a workspace that is too small or not 256-byte aligned; UAPS_ERANGE num_classes outside
+ *   [1, UAPS_MATCH_MAX_CLASSES], H * W >= 2^31, iou_threshold outside [0.5, 1) (NaN included), a pair matrix of
+ *   B * max_pred * max_gt * 4 bytes at or beyond 2 GiB.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_MATCH_MAX_CLASSES 64
+#define UAPS_MATCH_COLUMNS 4
+
+typedef struct uaps_match_call {
+    uint32_t struct_size;
+    int32_t B, H, W;
+    int32_t num_classes;
+    int32_t class_agnostic;                      /* 1: the class test is skipped */
+    double iou_threshold;                        /* in [0.5, 1) */
+    const int32_t* pred_labels;                  /* [B][H][W] */
+    const int32_t* target_labels;                /* [B][H][W] */
+    const int32_t* pred_count;                   /* [B] */
+    const int32_t* target_count;                 /* [B] */
+    const int64_t* pred_table;                   /* [B][max_pred][9] */
+    const int64_t* target_table;                 /* [B][max_gt][9] */
+    int32_t max_pred, max_gt;
+    int64_t* pred_out;                           /* [B][max_pred][4] */
+    int64_t* target_out;                         /* [B][max_gt][4] */
+    int64_t* counts;                             /* [B][num_classes][3] */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_match_call;
+int uaps_match_workspace_bytes(int B, int max_pred, int max_gt, size_t* bytes);
+int uaps_match_instances(const uaps_match_call* call);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,9 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
                                                     inference.predict_instances(..., tiled=True)
   surface_distances, distance_transform_sq, SurfaceResult, SURFACE_COLUMNS   boundary metrics on an exact device distance transform:
                                                     HD, HD95, ASSD, NSD under medpy's conventions; inference.evaluate(..., surface=True)
+  match_instances, MatchResult, MATCH_COLUMNS       defect matching against ground truth (two label_instances results): per-defect
+                                                    partner / IoU / covered, PQ, SQ, RQ, defect precision / recall, PRO;
+                                                    inference.evaluate(..., instances=True)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -62,6 +65,8 @@ from .tiled import predict_tiled, tile_plan, tile_window, tile_cut, tile_fold, T
 from . import tiled
 from .surface import surface_distances, distance_transform_sq, SurfaceResult, SURFACE_COLUMNS
 from . import surface
+from .matching import match_instances, MatchResult, MATCH_COLUMNS
+from . import matching
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -173,6 +173,8 @@ SIGNATURES = {
     "uaps_edt_sq": (C.c_int, [_PTR]),
     "uaps_surface_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
     "uaps_surface_distances": (C.c_int, [_PTR]),
+    "uaps_match_workspace_bytes": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_size_t)]),
+    "uaps_match_instances": (C.c_int, [_PTR]),
 }
 
 
@@ -381,6 +383,18 @@ class SurfaceCall(C.Structure):
                 ("pred_dtype", C.c_int32), ("target_dtype", C.c_int32), ("pred", C.c_void_p), ("pred_scores", C.c_void_p),
                 ("target", C.c_void_p), ("percentile_frac", C.c_double), ("has_tolerance", C.c_int32), ("tol_d2", C.c_int64),
                 ("table", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+MATCH_MAX_CLASSES, MATCH_COLUMNS = 64, 4  # UAPS_MATCH_MAX_CLASSES, UAPS_MATCH_COLUMNS
+
+
+class MatchCall(C.Structure):
+    """uaps_match_call (include/uaps_hip.h): every operand of uaps_match_instances, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("num_classes", C.c_int32),
+                ("class_agnostic", C.c_int32), ("iou_threshold", C.c_double), ("pred_labels", C.c_void_p), ("target_labels", C.c_void_p),
+                ("pred_count", C.c_void_p), ("target_count", C.c_void_p), ("pred_table", C.c_void_p), ("target_table", C.c_void_p),
+                ("max_pred", C.c_int32), ("max_gt", C.c_int32), ("pred_out", C.c_void_p), ("target_out", C.c_void_p),
+                ("counts", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
 SEG_NTERMS, SEG_MAX_CLASSES = 6, 8      # UAPS_SEG_NTERMS, UAPS_MAX_CLASSES

@@ -173,20 +173,50 @@ def _surface_sums(scored: torch.Tensor, y: torch.Tensor, kw) -> torch.Tensor:
     return torch.stack([total(r.hd95), total(r.assd), nsd, ok.sum().to(torch.float64)])
 
 
+_INSTANCE_KEYS = {"iou_threshold", "min_area", "connectivity", "max_instances", "classes"}
+
+
+def _instances_kwargs(instances):
+    """The keywords of an `instances` argument (True: the defaults)."""
+    if instances is True:
+        return {}
+    if not isinstance(instances, dict) or set(instances) - _INSTANCE_KEYS:
+        raise TypeError("evaluate: instances is True or a dict with the keywords " + ", ".join(sorted(_INSTANCE_KEYS)))
+    return dict(instances)
+
+
+def _instance_sums(scored: torch.Tensor, y: torch.Tensor, kw) -> torch.Tensor:
+    """float64 [K,7] on the device: matching.MatchResult.sums of one batch -- the defects of the arg-max of `scored` against the
+    defects of `y`, over the chosen classes (default 1 .. C-1)."""
+    from .instances import label_instances
+    from .matching import match_instances
+    lab = {k: kw[k] for k in ("min_area", "connectivity", "max_instances") if k in kw}
+    pred = label_instances(torch.argmax(scored, dim=1), **lab)
+    target = label_instances(y.to(torch.int64), **lab)
+    return match_instances(pred, target, scored.shape[1], iou_threshold=kw.get("iou_threshold", 0.5)).sums(kw.get("classes"))
+
+
 @torch.no_grad()
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None, tiled=None,
-             surface=None) -> Dict[str, float]:
+             surface=None, instances=None) -> Dict[str, float]:
     """The score table of notebook cell 25: mIoU, mDice and pixel accuracy of the main head computed image by image
     (utilities/metrics.py conventions) and averaged over the images, in percent.  tta=True, or a tuple of scales: the arg-max of the
     multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main head's.  tiled=True, or a dict of
     tiled.predict_tiled keywords: images of any size are scored on the blended probability maps of sliding-window inference.
     surface=True, or a dict with the keywords percentile, tolerance and classes: the boundary metrics of surface.surface_distances
     on the same scored maps are added -- "HD95(px)" and "ASSD(px)" (and "NSD(%)" with a tolerance), the means over the valid
-    (image, class) pairs of the whole run, and "surface_pairs", their number.  The pairs are summed on the device; one copy at the end."""
+    (image, class) pairs of the whole run, and "surface_pairs", their number.  The pairs are summed on the device; one copy at the end.
+    instances=True, or a dict with the keywords iou_threshold, min_area, connectivity, max_instances and classes: the defects of the
+    scored arg-max mask are matched against the defects of the labels (instances.label_instances on both, matching.match_instances)
+    and the per-defect scores are added -- "PQ(%)", "SQ(%)", "RQ(%)", "DefectPrecision(%)", "DefectRecall(%)", "PRO(%)" (the
+    overall values of matching.summarize), "defects_gt", "defects_pred" and "instance_images_skipped" (images with more defects than
+    max_instances on either side are left out).  Summed on the device; one copy at the end."""
     miou, mdice, acc = [], [], []
     tiled_kw = _tiled_kwargs(tiled, tta, "evaluate") if tiled else None
     surf_kw = _surface_kwargs(surface) if surface else None
     surf_sums = []
+    inst_kw = _instances_kwargs(instances) if instances else None
+    inst_sums = []
     for x, y in batches:
         if tiled_kw is not None:
             from .tiled import predict_tiled
@@ -198,6 +228,8 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
             scored = predict(model, x)[1][0]
         if surf_kw is not None:
             surf_sums.append(_surface_sums(scored, y, surf_kw))
+        if inst_kw is not None:
+            inst_sums.append(_instance_sums(scored, y, inst_kw))
         cms = metrics.seg_confusion_per_image(scored, y).cpu().numpy()
         for cm in cms:
             m = metrics.metrics_from_confusion(cm)
@@ -212,6 +244,17 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         if surf_kw.get("tolerance") is not None:
             out["NSD(%)"] = mean(tot[2]) * 100
         out["surface_pairs"] = pairs
+    if inst_kw is not None:
+        from .matching import SUM_COLUMNS, summarize
+        Cn = None if not inst_sums else inst_sums[0].shape[0]
+        classes = inst_kw.get("classes")
+        classes = list(range(1, (Cn or 0) + 1)) if classes is None else [int(c) for c in classes]
+        tot = torch.stack(inst_sums).sum(dim=0).cpu().numpy() if inst_sums else np.zeros((len(classes), len(SUM_COLUMNS)))
+        s = summarize(tot, classes, len(acc))
+        for key, name in (("PQ(%)", "PQ"), ("SQ(%)", "SQ"), ("RQ(%)", "RQ"), ("DefectPrecision(%)", "precision"),
+                          ("DefectRecall(%)", "recall"), ("PRO(%)", "PRO")):
+            out[key] = s[name] * 100
+        out["defects_gt"], out["defects_pred"], out["instance_images_skipped"] = s["n_gt"], s["n_pred"], s["images_skipped"]
     return out
 
 

@@ -220,7 +220,10 @@ int uaps_feat_mask_apply(const float* x, const uint8_t* keep, float scale, float
 
 /* FeatureDropout (UAPS_unet.py:161-169): y = x * (mean_c x < u * max_hw mean_c x), u = the
  * np.random.uniform(0.7, 0.9) draw.  keep [B,H,W] uint8 is written for the backward (dx = dy * keep).
- * workspace: uaps_feat_dropout_workspace_bytes(). */
+ * workspace: uaps_feat_dropout_workspace_bytes() bytes, 16-byte aligned -- the attention map inside it is read and written 16
+ * bytes at a time; uaps_feat_dropout_fwd, uaps_feat_dropout_stats and uaps_fanout_perturbed refuse any other workspace with
+ * UAPS_EINVAL and write nothing.  A pixel is kept when its attention is strictly below fl(max * u): a pixel at the threshold is
+ * dropped, an image whose attention is negative everywhere keeps every pixel, an all-zero image drops every pixel. */
 int uaps_feat_dropout_workspace_bytes(int B, int C, int H, int W, size_t* out_host);
 int uaps_feat_dropout_fwd(const float* x, float* y, int B, int C, int H, int W, float u, uint8_t* keep,
                           void* workspace, size_t workspace_bytes, uaps_stream_t stream);
@@ -319,7 +322,8 @@ int uaps_bn_act_bwd_eval(const float* dout, const float* y, const float* gamma, 
 
 /* UpBlock.forward lines 83-85: out[:, :Cs] = skip ; out[:, Cs:] = bilinear x2 (align_corners=True) of
  * low [B,Cl,h,w]; out is [B,Cs+Cl,2h,2w].  Backward: dskip = dout[:, :Cs] (may be NULL), dlow = the
- * transposed interpolation of dout[:, Cs:] (gather form, deterministic). */
+ * transposed interpolation of dout[:, Cs:] (gather form, deterministic).  No pointer needs an alignment beyond its
+ * element's: a dout, dskip or skip / out that is not 16-byte aligned takes the element-wise loads and stores. */
 int uaps_up_cat_fwd(const float* skip, const float* low, float* out, int B, int Cs, int Cl, int h, int w,
                     uaps_stream_t stream);
 int uaps_up_cat_bwd(const float* dout, float* dskip, float* dlow, int B, int Cs, int Cl, int h, int w,
@@ -946,7 +950,9 @@ int uaps_bin_confusion(const float* z, const int64_t* labels, int B, int H, int 
                        uaps_stream_t stream);
 
 /* Residual join of the ResNet blocks (utilities/resnet.py:47-50, 88-91): out = relu(a + b) over n floats; the
- * backward of both addends is dx = dout * (out > 0). */
+ * backward of both addends is dx = dout * (out > 0).  A NaN sum stays NaN, as torch.relu keeps it (and as the max-pool kernels
+ * propagate it); every other sum that is not above 0, -0.0 included, gives +0.0.  uaps_call_hints::out_amax is raised to the
+ * maximum of the outputs that are numbers: a NaN output does not enter it. */
 int uaps_add_relu(const float* a, const float* b, float* out, long n, uaps_stream_t stream);
 int uaps_relu_bwd(const float* dout, const float* out, float* dx, long n, uaps_stream_t stream);
 /* BatchNorm(train) + LeakyReLU backward in two halves (no dropout).  `prepare`: the reductions -- coef [groups][C][8] floats =

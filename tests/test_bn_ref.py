@@ -216,9 +216,14 @@ def test_backward_bars_reject_mutant(mut, cid, key):
 
 
 # ---- coverage --------------------------------------------------------------------------------------------------------------------
-def norm_act_kernel_symbols(so_path: str) -> set:
-    """The norm_act kernels (demangled, namespace stripped) in the gfx950 code objects of so_path (extracted as
-    tests/test_conv_form_table.py does)."""
+def kernel_pattern(names) -> "re.Pattern":
+    """Matches the demangled symbol of a kernel whose base name (template arguments apart) is one of `names`."""
+    return re.compile(r"^(?:void )?\(anonymous namespace\)::((?:" + "|".join(map(re.escape, names)) + r")(?:<[^>]*>)?)\(")
+
+
+def norm_act_kernel_symbols(so_path: str, pattern=_KERNEL) -> set:
+    """The kernels whose demangled symbol `pattern` matches (group 1: the name, namespace stripped; by default the norm_act
+    kernels) in the gfx950 code objects of so_path (extracted as tests/test_conv_form_table.py does)."""
     tmp = tempfile.mkdtemp(prefix="uaps_syms_")
     try:
         local = os.path.join(tmp, "lib.so")
@@ -234,7 +239,7 @@ def norm_act_kernel_symbols(so_path: str) -> set:
             for line in out.splitlines():
                 cols = line.split(None, 7)
                 if len(cols) == 8 and cols[3] == "FUNC":
-                    m = _KERNEL.match(cols[7].strip())
+                    m = pattern.match(cols[7].strip())
                     if m:
                         names.add(m.group(1))
         return names

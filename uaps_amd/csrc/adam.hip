@@ -59,6 +59,8 @@ extern "C" int uaps_adam_step(float* const* params, const float* const* grads, f
     // step < 1 with a step state set (uaps_set_step_state): lr / bias-correction1 and 1 / sqrt(bias-correction2) are read from it
     const void* st = uaps_get_step_state();
     if (!params || !grads || !exp_avg || !exp_avg_sq || !numel || n <= 0 || (step < 1 && !st)) return UAPS_EINVAL;
+    for (int k = 0; k < n; ++k)          // refuse before the first launch: a bad entry behind the first batch leaves every tensor as it was
+        if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k] || numel[k] <= 0) return UAPS_EINVAL;
     const double bc1 = 1.0 - pow(beta1, (double)(step < 1 ? 1 : step)), bc2 = 1.0 - pow(beta2, (double)(step < 1 ? 1 : step));
     const float step_size = step < 1 ? NAN : (float)(lr / bc1), inv_sqrt_bc2 = step < 1 ? NAN : (float)(1.0 / sqrt(bc2));
     for (int base = 0; base < n; base += kAdamBatch) {
@@ -67,7 +69,6 @@ extern "C" int uaps_adam_step(float* const* params, const float* const* grads, f
         long most = 0;
         for (int i = 0; i < m; ++i) {
             const int k = base + i;
-            if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k] || numel[k] <= 0) return UAPS_EINVAL;
             t.p[i] = params[k]; t.g[i] = grads[k]; t.m[i] = exp_avg[k]; t.v[i] = exp_avg_sq[k]; t.n[i] = numel[k];
             uaps::account_bytes(28.0 * numel[k]);          // p, g, m, v read; p, m, v written
             if (numel[k] > most) most = numel[k];

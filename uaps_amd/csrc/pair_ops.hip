@@ -267,19 +267,22 @@ extern "C" int uaps_entropy_map(const float* p, int B, int C, int H, int W, floa
 // ---- residual join of the ResNet blocks (utilities/resnet.py:47-50, 88-91): out = relu(a + b), and its backward
 // da = db = dout * (out > 0), each one 16-byte-per-lane streaming pass -------------------------------------------------
 namespace {
-// amax: optional bound (uaps_call_hints::out_amax) raised to max(out) -- the join's output feeds the next block's convolutions
+// relu as torch.relu: a NaN sum stays NaN (fmaxf(NaN, 0) would return 0), everything else that is not above 0 becomes +0
+__device__ __forceinline__ float relu_nan(float s) { return (s > 0.f || s != s) ? s : 0.f; }
+// amax: optional bound (uaps_call_hints::out_amax) raised to max(out) over the outputs that are numbers -- the join's output feeds
+// the next block's convolutions
 __global__ __launch_bounds__(kThreads) void add_relu_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                             float* __restrict__ out, long n4, long n, float* __restrict__ amax) {
     __shared__ float s16[16];
     float m = 0.f;
     for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (long)gridDim.x * kThreads) {
         const float4 x = reinterpret_cast<const float4*>(a)[i], y = reinterpret_cast<const float4*>(b)[i];
-        const float4 r = make_float4(fmaxf(x.x + y.x, 0.f), fmaxf(x.y + y.y, 0.f), fmaxf(x.z + y.z, 0.f), fmaxf(x.w + y.w, 0.f));
+        const float4 r = make_float4(relu_nan(x.x + y.x), relu_nan(x.y + y.y), relu_nan(x.z + y.z), relu_nan(x.w + y.w));
         reinterpret_cast<float4*>(out)[i] = r;
         m = fmaxf(m, fmaxf(fmaxf(r.x, r.y), fmaxf(r.z, r.w)));
     }
     if (blockIdx.x == 0)
-        for (long i = 4 * n4 + threadIdx.x; i < n; i += kThreads) { const float r = fmaxf(a[i] + b[i], 0.f); out[i] = r; m = fmaxf(m, r); }
+        for (long i = 4 * n4 + threadIdx.x; i < n; i += kThreads) { const float r = relu_nan(a[i] + b[i]); out[i] = r; m = fmaxf(m, r); }
     if (amax != nullptr) uaps::block_amax_to(amax, m, s16);
 }
 __global__ __launch_bounds__(kThreads) void relu_bwd_kernel(const float* __restrict__ dout, const float* __restrict__ out,

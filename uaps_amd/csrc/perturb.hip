@@ -533,6 +533,7 @@ extern "C" int uaps_feat_dropout_workspace_bytes(int B, int C, int H, int W, siz
 extern "C" int uaps_feat_dropout_fwd(const float* x, float* y, int B, int C, int H, int W, float u, uint8_t* keep,
                                      void* ws, size_t ws_bytes, uaps_stream_t stream) {
     if (!x || !y || !keep || !ws || B <= 0 || C <= 0 || H <= 0 || W <= 0) return UAPS_EINVAL;
+    if (!al16(ws)) return UAPS_EINVAL;      // the attention map at ws + round256(4 B) is read and written 16 bytes at a time
     size_t need; uaps_feat_dropout_workspace_bytes(B, C, H, W, &need);
     if (ws_bytes < need) return UAPS_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -570,6 +571,7 @@ extern "C" int uaps_feat_dropout_bwd(const float* dy, const uint8_t* keep, float
 // workspace of uaps_feat_dropout_workspace_bytes(B, ...) (what uaps_feat_dropout_fwd computes before it applies the mask).
 extern "C" int uaps_feat_dropout_stats(const float* x, int B, int C, int H, int W, void* ws, size_t ws_bytes, uaps_stream_t stream) {
     if (!x || !ws || B <= 0 || C <= 0 || H <= 0 || W <= 0) return UAPS_EINVAL;
+    if (!al16(ws)) return UAPS_EINVAL;      // the attention map at ws + round256(4 B) is read and written 16 bytes at a time
     size_t need; uaps_feat_dropout_workspace_bytes(B, C, H, W, &need);
     if (ws_bytes < need) return UAPS_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -613,6 +615,7 @@ extern "C" int uaps_fanout_perturbed(const float* f, float* const* out, const in
     }
     for (int q = 0; q < groups; ++q) a.u[q] = u ? u[q] : 0.f;
     if (fdrop_ws) {
+        if (!al16(fdrop_ws)) return UAPS_EINVAL;      // the attention map is read as float4
         a.maxkey = (const uint32_t*)fdrop_ws;
         a.att = (const float4*)((const char*)fdrop_ws + (((size_t)B * 4 + 255) / 256) * 256);
     }

@@ -163,7 +163,7 @@ __device__ __forceinline__ float tap_weight(float r, int o, int n_out, int n_in,
 template <int kLy>
 __global__ __launch_bounds__(kThreads) void up_cat_bwd_low_kernel(const float* __restrict__ dout, float* __restrict__ dlow, int B,
                                                                   int Cs, int Cl, int h, int w, float rh, float rw,
-                                                                  int tiles_x, int tiles_y) {
+                                                                  int tiles_x, int tiles_y, bool vec) {
     constexpr int kPr = 2 * kLy + 6;             // patch rows
     __shared__ __attribute__((aligned(16))) float sA[kPr * kPc];
     __shared__ float sT[kPr * kLx];
@@ -176,7 +176,6 @@ __global__ __launch_bounds__(kThreads) void up_cat_bwd_low_kernel(const float* _
     const int iy0 = ty * kLy, ix0 = tx * kLx;
     const int oy0 = 2 * iy0 - 3, ox0 = 2 * ix0 - 4;
     const float* p = dout + (((long)b * Ct + Cs + c) * H) * W;
-    const bool vec = (W % 4) == 0;
     // ---- stage the patch (zero outside the image) ----
     for (int u = threadIdx.x; u < kPr * (kPc / 4); u += kThreads) {
         const int r = u / (kPc / 4), x4 = (u % (kPc / 4)) * 4;
@@ -306,10 +305,11 @@ extern "C" int uaps_up_cat_bwd(const float* dout, float* dskip, float* dlow, int
             hipLaunchKernelGGL(slice_channels_kernel<false>, dim3(grid_for((long)B * Cs * HW)), dim3(kThreads), 0, s, dout, dskip, B, Cs + Cl, 0, Cs, HW);
     }
     const int ly = h >= 32 ? 32 : 8;
+    const bool vec = W % 4 == 0 && al16(dout);      // the patch rows as 16-byte loads: every plane and row of an aligned dout then is
     const int tiles_x = (w + kLx - 1) / kLx, tiles_y = (h + ly - 1) / ly;
     const long nblk = (long)B * Cl * tiles_x * tiles_y;
     if (nblk > 0x7fffffffL) return UAPS_ERANGE;
-    if (ly == 32) hipLaunchKernelGGL(up_cat_bwd_low_kernel<32>, dim3((unsigned)nblk), dim3(kThreads), 0, s, dout, dlow, B, Cs, Cl, h, w, rh, rw, tiles_x, tiles_y);
-    else hipLaunchKernelGGL(up_cat_bwd_low_kernel<8>, dim3((unsigned)nblk), dim3(kThreads), 0, s, dout, dlow, B, Cs, Cl, h, w, rh, rw, tiles_x, tiles_y);
+    if (ly == 32) hipLaunchKernelGGL(up_cat_bwd_low_kernel<32>, dim3((unsigned)nblk), dim3(kThreads), 0, s, dout, dlow, B, Cs, Cl, h, w, rh, rw, tiles_x, tiles_y, vec);
+    else hipLaunchKernelGGL(up_cat_bwd_low_kernel<8>, dim3((unsigned)nblk), dim3(kThreads), 0, s, dout, dlow, B, Cs, Cl, h, w, rh, rw, tiles_x, tiles_y, vec);
     return (int)hipGetLastError();
 }

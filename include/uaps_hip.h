@@ -140,6 +140,9 @@ const void* uaps_get_step_state(void);
  * fp32 NCHW, on the exact-f32 matrix instruction (csrc/conv_strided.hip).  They replace aten::convolution(_backward) and
  * aten::max_pool2d_with_indices(_backward) for those layers.  Packed weights: wf [ks*ks][Cin4][Cout16], wb [ks*ks][Cout4][Cin16]
  * (sizes in floats from uaps_convs_pack_floats).  Output size: OH = (H + 2 pad - ks) / stride + 1.
+ * Weight gradient: ks 1, 3, 7 (UAPS_ERANGE otherwise).  A 7x7 / 2 / 3 layer of <= 3 input channels whose OW % 4 == 0 runs the stem
+ * form when dy is 16-byte aligned and the general form otherwise; uaps_convs_wrw_workspace_bytes cannot see dy and reports the
+ * larger of the two needs, uaps_convs_bwd_weight checks workspace_bytes against the form it runs (UAPS_EWORKSPACE).
  * ------------------------------------------------------------------------------------------- */
 int uaps_convs_pack_floats(int Cout, int Cin, int ks, size_t* fwd_floats_host, size_t* bwd_floats_host);
 int uaps_convs_pack_weights(const float* w, int Cout, int Cin, int ks, float* wf, float* wb, uaps_stream_t stream);
@@ -152,7 +155,7 @@ int uaps_convs_wrw_workspace_bytes(int B, int Cin, int Cout, int H, int W, int k
 int uaps_convs_bwd_weight(const float* dy, const float* x, float* dw, int B, int Cin, int Cout, int H, int W, int ks, int stride,
                           int pad, void* workspace, size_t workspace_bytes, uaps_stream_t stream);
 /* planes = B*C; y [planes, OH, OW] with OH = (H - 1) / 2 + 1; idx: uint8 [planes, OH, OW], the window position of each arg-max
- * (first maximum wins, NaN propagates: torch.nn.MaxPool2d(3, 2, 1)) */
+ * (first maximum wins, a NaN replaces whatever is held, so of several NaNs the last: torch.nn.MaxPool2d(3, 2, 1)) */
 int uaps_maxpool3x3s2_fwd(const float* x, float* y, void* idx, long planes, int H, int W, uaps_stream_t stream);
 int uaps_maxpool3x3s2_bwd(const float* dy, const void* idx, float* dx, long planes, int H, int W, uaps_stream_t stream);
 /* y [planes, OH, OW] = x[:, ::2, ::2] (OH = (H - 1) / 2 + 1) and its adjoint (dx [planes, H, W]: dy at the even positions, zero

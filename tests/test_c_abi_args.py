@@ -163,6 +163,8 @@ def test_process_wide_switches_and_the_round3_plans(L):
     # the stem weight gradient (7x7 / 2 / 3, <= 3 input channels, OW % 4 == 0): 1024 splits of [64 channels][160 columns]
     assert L.uaps_convs_wrw_workspace_bytes(16, 3, 64, 640, 640, 7, 2, 3, C.byref(n)) == OK and n.value == 1024 * 64 * 160 * 4
     assert L.uaps_convs_wrw_workspace_bytes(2, 3, 64, 50, 70, 7, 2, 3, C.byref(n)) == OK and n.value % (49 * 64 * 16 * 4) == 0      # odd width: the general kernel's slabs
+    # a stem shape whose general form (run when dy is off 16 bytes, which the query cannot see) needs more than its stem form: the larger
+    assert L.uaps_convs_wrw_workspace_bytes(1, 1, 8, 9, 24, 7, 2, 3, C.byref(n)) == OK and n.value == 2 * 49 * 16 * 16 * 4 > 2 * 64 * 160 * 4
     fake = C.c_void_p(1 << 20)
     assert L.uaps_space_to_depth2(None, fake, 1, 8, 8, 8, 0, None) == EINVAL
     assert L.uaps_space_to_depth2(fake, fake, 1, 8, 7, 8, 0, None) == ERANGE             # odd height

@@ -1140,7 +1140,9 @@ def _s2d_index(dev):
 
 
 def conv3x3s2_supported(x: torch.Tensor) -> bool:
-    return x.is_cuda and x.shape[2] % 2 == 0 and x.shape[3] % 8 == 0
+    """What uaps_space_to_depth2 accepts: H even, W % 8 == 0 and a 16-byte aligned x.  A contiguous view at a storage offset
+    stays where it is (x.contiguous() returns it), so its own address counts; anything else is copied to a fresh, aligned tensor."""
+    return x.is_cuda and x.shape[2] % 2 == 0 and x.shape[3] % 8 == 0 and (not x.is_contiguous() or x.data_ptr() % 16 == 0)
 
 
 def conv3x3s2(x: torch.Tensor, weight: torch.Tensor, with_stats: bool = False):

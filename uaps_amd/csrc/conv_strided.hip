@@ -319,7 +319,8 @@ __global__ __launch_bounds__(256) void stem7_reduce_kernel(const float* __restri
 }
 
 // ---- 3x3 stride-2 pad-1 max-pool (utilities/resnet.py:124) ------------------------------------------------------------------
-// forward: y and the position (0..8, row-major in the window, first maximum wins like torch) of the arg-max of each window;
+// forward: y and the position (0..8, row-major in the window) of the arg-max of each window -- like torch the first maximum wins
+// and a NaN replaces whatever is held, so of several NaNs the last;
 // backward: every input pixel gathers the gradients of the <= 4 windows whose arg-max it is (fixed order, no atomics).
 __global__ __launch_bounds__(256) void maxpool3s2_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, uint8_t* __restrict__ idx,
                                                              long planes, int H, int W, int OH, int OW) {
@@ -338,7 +339,7 @@ __global__ __launch_bounds__(256) void maxpool3s2_fwd_kernel(const float* __rest
                 const int iy = oy * 2 + ky - 1, ix = ox * 2 + kx - 1;
                 if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
                 const float v = xp[(long)iy * W + ix];
-                if (!any || v > best || (v != v && best == best)) { best = v; bi = ky * 3 + kx; any = true; }     // NaN propagates like torch
+                if (!any || v > best || v != v) { best = v; bi = ky * 3 + kx; any = true; }     // every NaN is taken, like torch
             }
         y[e] = best;
         idx[e] = (uint8_t)bi;
@@ -447,10 +448,13 @@ extern "C" int uaps_convs_bwd_data(const float* dy, const float* wb, float* dx, 
 
 namespace {
 struct SWrwPlan { int CoutS, CinS, ncob, ncib, nsplit, tiles_x, tiles_y; bool stem; };
-SWrwPlan plan_swrw(int B, int Cin, int Cout, int OH, int OW, int ks, int stride = 1, int pad = 0) {
+// the shapes of the stem form (stem7_wrw_kernel): 7x7 / 2 / 3, <= 3 input channels, 16-byte rows of dy.  Whether a call runs it
+// also depends on dy's alignment, which only uaps_convs_bwd_weight sees.
+inline bool stem_shape(int Cin, int OW, int ks, int stride, int pad) { return ks == 7 && stride == 2 && pad == 3 && Cin <= 3 && OW % 4 == 0; }
+// stem: plan the stem form (the caller has checked stem_shape and, where it launches, the alignment of dy); otherwise the general form
+SWrwPlan plan_swrw(int B, int Cin, int Cout, int OH, int OW, int ks, bool stem) {
     SWrwPlan p{};
-    // the stem form (stem7_wrw_kernel): 7x7 / 2 / 3, <= 3 input channels, 16-byte rows of dy
-    p.stem = ks == 7 && stride == 2 && pad == 3 && Cin <= 3 && OW % 4 == 0;
+    p.stem = stem;
     if (p.stem) {
         p.ncob = (Cout + 63) / 64; p.ncib = 1;
         p.CoutS = p.ncob * 64; p.CinS = kStemN;
@@ -471,14 +475,23 @@ SWrwPlan plan_swrw(int B, int Cin, int Cout, int OH, int OW, int ks, int stride 
     p.nsplit = (int)want;
     return p;
 }
+// the slab floats the plan's kernel writes: [nsplit][CoutS][160] (stem) or [nsplit][taps][CoutS][CinS]
+inline size_t plan_bytes(const SWrwPlan& p, int ks) { return (size_t)p.nsplit * (p.stem ? 1 : ks * ks) * p.CoutS * p.CinS * sizeof(float); }
 }  // namespace
 
+// The query cannot see dy: where the shape admits the stem form it reports the larger of the two plans' needs, so that the
+// workspace serves whichever form uaps_convs_bwd_weight then runs.
 extern "C" int uaps_convs_wrw_workspace_bytes(int B, int Cin, int Cout, int H, int W, int ks, int stride, int pad, size_t* out) {
     if (!out) return UAPS_EINVAL;
     int rc = check_sconv(B, Cin, Cout, H, W, ks, stride, pad);
     if (rc) return rc;
-    const SWrwPlan p = plan_swrw(B, Cin, Cout, (H + 2 * pad - ks) / stride + 1, (W + 2 * pad - ks) / stride + 1, ks, stride, pad);
-    *out = (size_t)p.nsplit * (p.stem ? 1 : ks * ks) * p.CoutS * p.CinS * sizeof(float);
+    const int OH = (H + 2 * pad - ks) / stride + 1, OW = (W + 2 * pad - ks) / stride + 1;
+    size_t n = plan_bytes(plan_swrw(B, Cin, Cout, OH, OW, ks, false), ks);
+    if (stem_shape(Cin, OW, ks, stride, pad)) {
+        const size_t ns = plan_bytes(plan_swrw(B, Cin, Cout, OH, OW, ks, true), ks);
+        if (ns > n) n = ns;
+    }
+    *out = n;
     return UAPS_OK;
 }
 
@@ -490,9 +503,10 @@ extern "C" int uaps_convs_bwd_weight(const float* dy, const float* x, float* dw,
     if (rc) return rc;
     if (ks != 1 && ks != 3 && ks != 7) return UAPS_ERANGE;
     const int OH = (H + 2 * pad - ks) / stride + 1, OW = (W + 2 * pad - ks) / stride + 1;
-    const SWrwPlan p = plan_swrw(B, Cin, Cout, OH, OW, ks, stride, pad);
-    if (ws_bytes < (size_t)p.nsplit * (p.stem ? 1 : ks * ks) * p.CoutS * p.CinS * sizeof(float)) return UAPS_EWORKSPACE;
-    if (p.stem && (uintptr_t)dy % 16 == 0) {
+    // shape and alignment together decide the form, and the plan (blocks, slab strides, workspace) is that form's own
+    const SWrwPlan p = plan_swrw(B, Cin, Cout, OH, OW, ks, stem_shape(Cin, OW, ks, stride, pad) && (uintptr_t)dy % 16 == 0);
+    if (ws_bytes < plan_bytes(p, ks)) return UAPS_EWORKSPACE;
+    if (p.stem) {
         StemWrwArgs sa{dy, x, (float*)ws, B, Cin, Cout, H, W, OH, OW, p.CoutS, p.nsplit, p.tiles_x, p.tiles_y};
         UAPS_LAUNCH_MAIN(stem7_wrw_kernel, dim3((unsigned)p.nsplit, (unsigned)p.ncob), dim3(256), 0, (hipStream_t)stream, sa);
         hipError_t e0 = hipGetLastError();

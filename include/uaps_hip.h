@@ -1485,6 +1485,95 @@ typedef struct uaps_match_call {
 int uaps_match_workspace_bytes(int B, int max_pred, int max_gt, size_t* bytes);
 int uaps_match_instances(const uaps_match_call* call);
 
+/* ---------------------------------------------------------------------------------------------
+ * Threshold-sweep histograms: csrc/curves.hip.  Per image and row the histogram of quantised scores split by a binary event -- the one
+ * primitive AUROC, average precision, AUPRO, ECE and AURC are formed from (uaps_amd/curves.py does that on the host, in float64).
+ * Integers throughout, pro_sum aside (float64, summed in a fixed order): exact, and the same bits from run to run.
+ *
+ *   Bin rule   inv = (float) bins / ((float) hi - (float) lo), formed once on the host in fp32;
+ *              bin(s) = clamp(floor((s - lo) * inv), 0, bins - 1): subtraction and product rounded separately in fp32 (no fma), the clamp
+ *              in float before the conversion.  +inf and everything >= hi land in the last bin, -inf and everything < lo in bin 0; a NaN
+ *              enters no bin and is counted in `nan`.  2 <= bins <= UAPS_CURVES_MAX_BINS.
+ *   Rows       uaps_score_curves forms R = n_classes + top_row rows per image from one read of scores fp32 [B, C, H, W]:
+ *              class row k: score = S[b, classes[k], y, x], event = (target == classes[k]);
+ *              top row (C >= 2): score = max_c S[b, c], event = (arg-max_c == target), the lowest index among equal values, taken on
+ *                the logits with from_logits; its score is NaN where any of the pixel's C scores is.
+ *              A pixel whose target lies outside [0, C) enters no row and no counter.  from_logits == 1: the softmax over the pixel's C
+ *              values is formed in registers first.  C == 1 is the sigmoid head: the plane is the score p of class 1
+ *              (1 / (1 + expf(-z)) with from_logits), classes is {1}, event = (target == 1), targets outside {0, 1} are ignored; its top
+ *              row is score = max(p, 1 - p), event = ((p > 0.5) == target), z > 0 with from_logits.
+ *   Plane      uaps_plane_curves: score fp32 [B, H, W] with its own lo / hi, pred and target label maps; one row, event = (pred == target);
+ *              pixels with target < 0 are ignored.
+ *   Outputs    (the call zeroes them itself) hist int64 [B, R, 2, bins], index 0 = event false, 1 = true; qsum int64 [B, R, 2, bins] or
+ *              NULL: the sum over the cell's pixels of q(s) = (int64) rintf(clamp(s, -65536, 65536) * 2^24), the fixed point of
+ *              uaps_label_instances; nan int64 [B, R].
+ *   Regions    optional, all of region_labels / region_count / region_table (a uaps_label_instances result of the ground truth with
+ *              max_regions rows), pro_sum, n_regions and the workspace, or none.  A pixel with region label g in [1, max_regions] whose
+ *              region class c = table[b, g - 1, 0] lies in [0, C) (C == 1: equals 1) adds one to region_hist[b, g - 1, bin(S[b, c, y, x])]
+ *              (int32 [B, max_regions, bins] in the workspace; only the rows below min(count[b], max_regions) are zeroed and used, the
+ *              bound is read on the device).  Then pro_sum float64 [B, n_classes, bins]: pro_sum[b, k, i] = the sum over the regions r of
+ *              image b whose class is classes[k], in ascending r, of (double) suffix_r(i) / (double) area_r, suffix_r(i) = sum over
+ *              j >= i of region_hist[b, r, j], area_r = table[b, r, 1]; n_regions int64 [B, n_classes] their number.
+ *   Launches: zero; one pass over the scores (four pixels a lane with 16-byte loads where H * W % 4 == 0 and the tensors are 16-byte
+ *   aligned, rows privatised in at most 64 KB of LDS as 32-bit counters, lanes of a wave with one key counted by ballot, non-zero words
+ *   flushed with 64-bit integer atomics; rows that do not fit are processed in groups along the grid's second dimension); with regions
+ *   the reduction.  Integer atomics only, nothing waits inside a launch; the call does not synchronise.
+ *   workspace: uaps_curves_workspace_bytes(B, max_regions, bins) bytes (0 without regions), 256-byte aligned, the call's alone until it
+ *   has run.
+ * Both structs are size-versioned (fields are only ever appended; a larger struct_size is accepted and what it appends is not read).
+ * Errors (nothing launched): UAPS_EINVAL null struct or a pointer the call uses, non-positive dimension, struct_size below this
+ *   version's, unknown dtype, from_logits or top_row outside {0, 1}, from_logits in plane mode, n_classes + top_row == 0 or n_classes
+ *   outside [0, UAPS_MAX_CLASSES], a class outside [0, C) (C == 1: other than 1), lo >= hi or a non-finite bound (or a range so narrow
+ *   that inv is not finite), regions without all of their operands, a workspace that is too small or not 256-byte aligned;
+ *   UAPS_ERANGE C outside [1, UAPS_MAX_CLASSES], bins outside [2, UAPS_CURVES_MAX_BINS], H * W >= 2^31, any tensor or the workspace
+ *   at or beyond 2 GiB (by dimensions).
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_CURVES_MAX_BINS 4096
+
+typedef struct uaps_curves_call {
+    uint32_t struct_size;
+    int32_t B, C, H, W;
+    int32_t bins;
+    int32_t from_logits, top_row;
+    int32_t n_classes;
+    int32_t classes[UAPS_MAX_CLASSES];
+    int32_t target_dtype;                        /* UAPS_LABEL_* */
+    float lo, hi;
+    const float* scores;                         /* [B][C][H][W] */
+    const void* target;                          /* [B][H][W] */
+    const int32_t* region_labels;                /* [B][H][W] or NULL */
+    const int32_t* region_count;                 /* [B] */
+    const int64_t* region_table;                 /* [B][max_regions][9] */
+    int32_t max_regions;
+    int64_t* hist;                               /* [B][R][2][bins] */
+    int64_t* qsum;                               /* [B][R][2][bins] or NULL */
+    int64_t* nan;                                /* [B][R] */
+    double* pro_sum;                             /* [B][n_classes][bins], with regions */
+    int64_t* n_regions;                          /* [B][n_classes], with regions */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_curves_call;
+int uaps_curves_workspace_bytes(int B, int max_regions, int bins, size_t* bytes);
+int uaps_score_curves(const uaps_curves_call* call);
+
+typedef struct uaps_plane_curves_call {
+    uint32_t struct_size;
+    int32_t B, H, W;
+    int32_t bins;
+    int32_t from_logits;                         /* must be 0 */
+    int32_t pred_dtype, target_dtype;            /* UAPS_LABEL_* */
+    float lo, hi;
+    const float* score;                          /* [B][H][W] */
+    const void* pred;                            /* [B][H][W] */
+    const void* target;                          /* [B][H][W] */
+    int64_t* hist;                               /* [B][1][2][bins] */
+    int64_t* qsum;                               /* [B][1][2][bins] or NULL */
+    int64_t* nan;                                /* [B][1] */
+    uaps_stream_t stream;
+} uaps_plane_curves_call;
+int uaps_plane_curves(const uaps_plane_curves_call* call);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,9 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   match_instances, MatchResult, MATCH_COLUMNS       defect matching against ground truth (two label_instances results): per-defect
                                                     partner / IoU / covered, PQ, SQ, RQ, defect precision / recall, PRO;
                                                     inference.evaluate(..., instances=True)
+  score_curves, plane_curves, CurveResult, CurveSums  threshold-sweep metrics from histograms of quantised scores: pixel AUROC, AP,
+                                                    AUPRO, ECE, and AUROC / AURC of the uncertainty map;
+                                                    inference.evaluate(..., curves=True)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -67,6 +70,8 @@ from .surface import surface_distances, distance_transform_sq, SurfaceResult, SU
 from . import surface
 from .matching import match_instances, MatchResult, MATCH_COLUMNS
 from . import matching
+from .curves import score_curves, plane_curves, CurveResult, CurveSums
+from . import curves
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

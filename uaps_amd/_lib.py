@@ -175,6 +175,9 @@ SIGNATURES = {
     "uaps_surface_distances": (C.c_int, [_PTR]),
     "uaps_match_workspace_bytes": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_size_t)]),
     "uaps_match_instances": (C.c_int, [_PTR]),
+    "uaps_curves_workspace_bytes": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_size_t)]),
+    "uaps_score_curves": (C.c_int, [_PTR]),
+    "uaps_plane_curves": (C.c_int, [_PTR]),
 }
 
 
@@ -395,6 +398,27 @@ class MatchCall(C.Structure):
                 ("pred_count", C.c_void_p), ("target_count", C.c_void_p), ("pred_table", C.c_void_p), ("target_table", C.c_void_p),
                 ("max_pred", C.c_int32), ("max_gt", C.c_int32), ("pred_out", C.c_void_p), ("target_out", C.c_void_p),
                 ("counts", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+CURVES_MAX_BINS = 4096                  # UAPS_CURVES_MAX_BINS
+
+
+class CurvesCall(C.Structure):
+    """uaps_curves_call (include/uaps_hip.h): every operand of uaps_score_curves, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("bins", C.c_int32),
+                ("from_logits", C.c_int32), ("top_row", C.c_int32), ("n_classes", C.c_int32), ("classes", C.c_int32 * 8),
+                ("target_dtype", C.c_int32), ("lo", C.c_float), ("hi", C.c_float), ("scores", C.c_void_p), ("target", C.c_void_p),
+                ("region_labels", C.c_void_p), ("region_count", C.c_void_p), ("region_table", C.c_void_p), ("max_regions", C.c_int32),
+                ("hist", C.c_void_p), ("qsum", C.c_void_p), ("nan", C.c_void_p), ("pro_sum", C.c_void_p), ("n_regions", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class PlaneCurvesCall(C.Structure):
+    """uaps_plane_curves_call (include/uaps_hip.h): every operand of uaps_plane_curves, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("bins", C.c_int32),
+                ("from_logits", C.c_int32), ("pred_dtype", C.c_int32), ("target_dtype", C.c_int32), ("lo", C.c_float), ("hi", C.c_float),
+                ("score", C.c_void_p), ("pred", C.c_void_p), ("target", C.c_void_p), ("hist", C.c_void_p), ("qsum", C.c_void_p),
+                ("nan", C.c_void_p), ("stream", C.c_void_p)]
 
 
 SEG_NTERMS, SEG_MAX_CLASSES = 6, 8      # UAPS_SEG_NTERMS, UAPS_MAX_CLASSES

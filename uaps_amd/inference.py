@@ -196,9 +196,44 @@ def _instance_sums(scored: torch.Tensor, y: torch.Tensor, kw) -> torch.Tensor:
     return match_instances(pred, target, scored.shape[1], iou_threshold=kw.get("iou_threshold", 0.5)).sums(kw.get("classes"))
 
 
+_CURVE_KEYS = {"bins", "fpr_limit", "ece_bins", "classes", "max_instances", "connectivity", "min_area", "uncertainty", "lo", "hi"}
+
+
+def _curves_kwargs(curves, tta, tiled):
+    """The keywords of a `curves` argument (True: the defaults)."""
+    if curves is True:
+        return {}
+    if not isinstance(curves, dict) or set(curves) - _CURVE_KEYS:
+        raise TypeError("evaluate: curves is True or a dict with the keywords " + ", ".join(sorted(_CURVE_KEYS)))
+    if curves.get("uncertainty") and (tta or tiled):
+        raise ValueError("evaluate: curves with uncertainty=True scores the plain forward's uncertainty map: not built under tta or tiled")
+    return dict(curves)
+
+
+def _curve_sums(scored: torch.Tensor, y: torch.Tensor, kw, from_logits: bool):
+    """curves.CurveResult.sums of one batch: the class rows (default 1 .. C-1), the top row with its fixed-point sums, and the regions
+    of the labels' defects."""
+    from .curves import score_curves
+    from .instances import label_instances
+    lab = {k: kw[k] for k in ("min_area", "connectivity", "max_instances") if k in kw}
+    regions = label_instances(y.to(torch.int64), **lab)
+    return score_curves(scored.float(), y, classes=kw.get("classes"), bins=kw.get("bins", 1024), top=True, from_logits=from_logits,
+                        regions=regions, want_sums=True).sums()
+
+
+def _uncertainty_sums(heads, y: torch.Tensor, kw):
+    """The sums of curves.plane_curves on consistency.uncertainty_map(main, aux1) against "the main head's arg-max is right"."""
+    from .curves import plane_curves
+    if len(heads) < 2:
+        raise ValueError("evaluate: curves with uncertainty=True needs a model with an auxiliary head")
+    unc = consistency.uncertainty_map(heads[0], heads[1])
+    return plane_curves(unc.float(), torch.argmax(heads[0], dim=1), y, bins=kw.get("bins", 1024), lo=kw.get("lo", 0.0),
+                        hi=kw.get("hi", 1.0)).sums()
+
+
 @torch.no_grad()
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None, tiled=None,
-             surface=None, instances=None) -> Dict[str, float]:
+             surface=None, instances=None, curves=None) -> Dict[str, float]:
     """The score table of notebook cell 25: mIoU, mDice and pixel accuracy of the main head computed image by image
     (utilities/metrics.py conventions) and averaged over the images, in percent.  tta=True, or a tuple of scales: the arg-max of the
     multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main head's.  tiled=True, or a dict of
@@ -210,8 +245,17 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     scored arg-max mask are matched against the defects of the labels (instances.label_instances on both, matching.match_instances)
     and the per-defect scores are added -- "PQ(%)", "SQ(%)", "RQ(%)", "DefectPrecision(%)", "DefectRecall(%)", "PRO(%)" (the
     overall values of matching.summarize), "defects_gt", "defects_pred" and "instance_images_skipped" (images with more defects than
-    max_instances on either side are left out).  Summed on the device; one copy at the end."""
+    max_instances on either side are left out).  Summed on the device; one copy at the end.
+    curves=True, or a dict (an empty one: the defaults) with the keywords bins, fpr_limit, ece_bins, classes, max_instances, connectivity, min_area, uncertainty, lo
+    and hi: the threshold-sweep scores of curves.score_curves on the scored maps (the logits of the plain path go through the kernel's
+    softmax; under tta and tiled the maps are probabilities already) are added -- "AUROC(%)", "AP(%)", "AUPRO(%)" (up to fpr_limit,
+    default 0.3, over the defects of the labels), "ECE(%)" (ece_bins groups, default 16) and "curve_images_skipped" (images with more
+    real defects than max_instances are left out).  uncertainty=True (plain path only, a model with an auxiliary head) adds
+    "UncAUROC(%)" and "AURC": how well consistency.uncertainty_map(main, aux1), binned over [lo, hi] (default 0, 1), marks the wrong
+    pixels of the main head.  Summed on the device; one copy at the end."""
     miou, mdice, acc = [], [], []
+    curve_kw = _curves_kwargs(curves, tta, tiled) if curves is not None and curves is not False else None      # ({}: the defaults)
+    curve_sums = unc_sums = None
     tiled_kw = _tiled_kwargs(tiled, tta, "evaluate") if tiled else None
     surf_kw = _surface_kwargs(surface) if surface else None
     surf_sums = []
@@ -225,7 +269,14 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
             from .tta import DEFAULT_SCALES, predict_tta
             scored = predict_tta(model, x, scales=DEFAULT_SCALES if tta is True else tuple(tta), want=("probs",)).probs
         else:
-            scored = predict(model, x)[1][0]
+            heads = predict(model, x)[1]
+            scored = heads[0]
+            if curve_kw is not None and curve_kw.get("uncertainty"):
+                part = _uncertainty_sums(heads, y, curve_kw)
+                unc_sums = part if unc_sums is None else unc_sums + part
+        if curve_kw is not None:
+            part = _curve_sums(scored, y, curve_kw, from_logits=tiled_kw is None and not tta)
+            curve_sums = part if curve_sums is None else curve_sums + part
         if surf_kw is not None:
             surf_sums.append(_surface_sums(scored, y, surf_kw))
         if inst_kw is not None:
@@ -255,6 +306,23 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
                           ("DefectRecall(%)", "recall"), ("PRO(%)", "PRO")):
             out[key] = s[name] * 100
         out["defects_gt"], out["defects_pred"], out["instance_images_skipped"] = s["n_gt"], s["n_pred"], s["images_skipped"]
+    if curve_kw is not None:
+        from .curves import summarize as curve_summarize
+        nan = float("nan")
+        s = {"AUROC": nan, "AP": nan, "AUPRO": nan, "ECE": nan, "images_skipped": 0}
+        if curve_sums is not None:
+            Cn = curve_sums.hist.shape[0]                     # the class rows and the top row
+            classes = curve_kw.get("classes")
+            classes = list(range(1, Cn)) if classes is None else [int(c) for c in classes]
+            s = curve_summarize(curve_sums, classes, fpr_limit=curve_kw.get("fpr_limit", 0.3), ece_bins=curve_kw.get("ece_bins", 16))
+        for key in ("AUROC", "AP", "AUPRO", "ECE"):
+            out[key + "(%)"] = s[key] * 100
+        out["curve_images_skipped"] = s["images_skipped"]
+        if curve_kw.get("uncertainty"):
+            u = {"AUROC": nan, "AURC": nan}
+            if unc_sums is not None:
+                u = curve_summarize(unc_sums, (), lo=curve_kw.get("lo", 0.0), hi=curve_kw.get("hi", 1.0), plane=True)
+            out["UncAUROC(%)"], out["AURC"] = u["AUROC"] * 100, u["AURC"]
     return out
 
 

@@ -78,6 +78,49 @@ def test_mc_consistency_refuses_bad_arguments(L):
     assert bwd(B=128, Cc=8, H=1024, W=1024) == ERANGE
 
 
+def test_pair_ops_refuse_bad_arguments(L):
+    """The sibling consistency terms of pair_ops.hip (include/uaps_hip.h: C in [2, 8], any output may be NULL, the workspace is
+    needed for a mean only).  Their header block promises no 2 GiB refusal, and they make none: the kernels index with 64-bit offsets."""
+    n = C.c_size_t()
+    assert L.uaps_pair_workspace_bytes(C.byref(n)) == 0 and n.value >= 4
+    assert L.uaps_pair_workspace_bytes(None) == EINVAL
+    ws = n.value
+
+    def fwd(a=P, b=P, probs=0, B=2, Cc=4, H=8, W=8, mse=P, klm=P, mean=P, w=P, wb=None):
+        return L.uaps_softmax_pair_fwd(a, b, probs, B, Cc, H, W, mse, klm, mean, w, ws if wb is None else wb, None)
+    for bad in ({"a": None}, {"b": None}, {"B": 0}, {"H": 0}, {"W": -1}, {"mse": None, "klm": None, "mean": None}):
+        assert fwd(**bad) == EINVAL, bad
+        assert fwd(probs=1, **bad) == EINVAL, bad
+    assert fwd(Cc=1) == ERANGE and fwd(Cc=9) == ERANGE
+    assert fwd(w=None) == EWORKSPACE and fwd(wb=ws - 1) == EWORKSPACE
+    assert fwd(Cc=9, w=None) == ERANGE                      # the class count is looked at before the workspace
+
+    def mse(a=P, b=P, g=P, B=2, Cc=4, H=8, W=8, da=P):
+        return L.uaps_softmax_mse_bwd(a, b, g, B, Cc, H, W, da, None)
+    for bad in ({"a": None}, {"b": None}, {"g": None}, {"da": None}, {"B": 0}, {"H": -1}, {"W": 0}):
+        assert mse(**bad) == EINVAL, bad
+    assert mse(Cc=1) == ERANGE and mse(Cc=9) == ERANGE
+
+    def kl(a=P, b=P, g=P, B=2, Cc=4, H=8, W=8, da=P):
+        return L.uaps_softmax_kl_bwd(a, b, g, B, Cc, H, W, da, None)
+    for bad in ({"a": None}, {"b": None}, {"da": None}, {"B": -1}, {"H": 0}, {"W": 0}, {"g": None, "B": 0}):
+        assert kl(**bad) == EINVAL, bad
+    assert kl(Cc=1) == ERANGE and kl(Cc=9, g=None) == ERANGE
+
+    def klmap(a=P, b=P, g=P, B=2, Cc=4, H=8, W=8, da=P, db=P):
+        return L.uaps_softmax_klmap_bwd(a, b, g, B, Cc, H, W, da, db, None)
+    for bad in ({"a": None}, {"b": None}, {"g": None}, {"da": None, "db": None}, {"B": 0}, {"H": 0}, {"W": -3}):
+        assert klmap(**bad) == EINVAL, bad
+    assert klmap(Cc=1, db=None) == ERANGE and klmap(Cc=9, da=None) == ERANGE
+
+    def ent(p=P, B=2, Cc=4, H=8, W=8, m=P, mean=P, w=P, wb=None):
+        return L.uaps_entropy_map(p, B, Cc, H, W, m, mean, w, ws if wb is None else wb, None)
+    for bad in ({"p": None}, {"B": 0}, {"H": 0}, {"W": 0}, {"m": None, "mean": None}):
+        assert ent(**bad) == EINVAL, bad
+    assert ent(Cc=1) == ERANGE and ent(Cc=9) == ERANGE
+    assert ent(w=None) == EWORKSPACE and ent(wb=0) == EWORKSPACE and ent(m=None, wb=ws - 1) == EWORKSPACE
+
+
 def test_ema_alpha_schedule():
     from uaps_amd.mean_teacher import ema_alpha
     assert ema_alpha(0.99, 0) == (0.0, 1.0)                   # step 0: the teacher becomes a copy of the student

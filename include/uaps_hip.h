@@ -992,6 +992,27 @@ int uaps_head_bwd_fused(const float* dlogits, const float* y, const void* xf, fl
                         int H, int W, int ks, int cfg, float* g, void* partials, float* maxes, void* workspace,
                         size_t workspace_bytes, uaps_stream_t stream);
 
+/* The backward of the second convolution of a decoder ConvBlock and the reductions of the BatchNorm in front of it as ONE pass
+ * (csrc/mid_bwd_row.hip) where uaps_conv_bwd_weight_partial_bn with uaps_call_hints::dyt_*, uaps_conv_bwd_data and the sums pass of
+ * uaps_bn_act_bwd_prepare ran one after the other.  dact [B,Cout,H,W] is the gradient behind the BatchNorm + LeakyReLU that follows
+ * z = conv(leaky_relu(batch_norm_train(y1)), w), its transform pending: y2 = z [B,Cout,H,W] raw, coef [groups2][Cout][8] from
+ * uaps_bn_act_bwd_prepare / _finalize, slope2 that LeakyReLU's slope; y1 [B,Cin,H,W] is the raw output of the convolution in front and
+ * xf [groups][Cin] float2 (scale, shift) from uaps_bn_finalize_train; wb the packed input-gradient weights of w.  The true dz is formed
+ * on the way and NOT written.  Written: g [B,Cin,H,W] = d(activation), bit-identical to uaps_conv_bwd_data's on the written-through
+ * dz; the per-split slabs of dw (and dbias with want_bias) in the workspace layout uaps_conv_wrw_workspace_bytes(B, Cin, Cout, H, W,
+ * ks, cfg) reports, bit-identical to uaps_conv_bwd_weight_partial_bn's; partials float2 [Cin][B][H / 16] and maxes (two bounds, zeroed
+ * by the caller) as uaps_head_bwd_fused writes them, for uaps_bn_act_bwd_finalize(partials, H / 16, maxes, ...).  dy_bound / x_bound
+ * (times their host factors) bound |dz| and the activation.  Only enqueues on `stream`; no float atomics, two launches give the same
+ * bits.
+ * One form: ks == 3, Cin == Cout == 16, W == 256, H % 16 == 0, mode 2 (fp16-split arithmetic) with both bounds present, a pending
+ * transform (y2 and coef), 16-byte aligned tensors, cfg without dilation / exact / split bits, the row weight-gradient kernels not
+ * tuned off.  Anything else returns UAPS_ENOFORM with nothing launched: make the three separate calls. */
+int uaps_mid_bwd_fused(const float* dact, const float* y2, const float* coef, float slope2, int groups2, const float* y1,
+                       const void* xf, float slope, int groups, const float* wb, const float* dy_bound, float dy_mul,
+                       const float* x_bound, float x_mul, const float* save_mean, const float* save_invstd, const float* gamma,
+                       const float* beta, int want_bias, int B, int Cin, int Cout, int H, int W, int ks, int cfg, float* g,
+                       void* partials, float* maxes, void* workspace, size_t workspace_bytes, uaps_stream_t stream);
+
 /* The same when the join's output had k <= 4 consumers: dx = (dout[0] + ... + dout[k-1]) * (out > 0), the k gradients (host
  * array of device pointers) summed in order by this pass instead of by k - 1 accumulation passes in front of it. */
 int uaps_relu_bwd_sum(const float* const* dout_host, int k, const float* out, float* dx, long n, uaps_stream_t stream);

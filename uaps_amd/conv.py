@@ -645,14 +645,23 @@ def conv_fwd_raw(x: torch.Tensor, wf: torch.Tensor, bias: Optional[torch.Tensor]
 _FUSED_BSUM = config.flag("UAPS_FUSED_BN_SUMS", False)
 
 
-def conv_bwd_data_raw(dy: torch.Tensor, wb: torch.Tensor, Cin: int, ks: int, cfg: int = 0, dyb=None, bsum=None, head=None):
+def conv_bwd_data_raw(dy: torch.Tensor, wb: torch.Tensor, Cin: int, ks: int, cfg: int = 0, dyb=None, bsum=None, head=None, mid=None):
     """bsum = (y, mean, invstd, gamma, beta, slope, groups): dx is d(activation) of the train-mode BatchNorm + LeakyReLU whose raw
     input is y; where the layer's kernel can (uaps_call_hints::bsum_*), its epilogue also forms that BatchNorm's backward sums --
     then (dx, partials, maxes) comes back for lazybn.prepare_from_partials, else (dx, None, None).
     head = (xf, xb, want_bias, ws), with bsum: the caller also wants this convolution's weight gradient, whose input is
     leaky_relu(fma(y, xf)) bounded by xb; where the one-pass kernel of out_conv's backward has the form (head_bwd_fused) it forms dx,
     the sums and the weight-gradient slabs in `ws` together, and a fourth value says whether it did (True: follow with _wrw_reduce;
-    False: nothing of the weight gradient was computed)."""
+    False: nothing of the weight gradient was computed).
+    mid = (lz, xf, xb, want_bias, ws), with bsum: `dy` is d(activation) behind the BatchNorm that follows this convolution, its
+    transform lz (lazybn.Lazy) pending, and the caller wants the weight gradient too: the one-pass kernel of a ConvBlock's second
+    convolution (mid_bwd_fused) forms the true dy on the way, and from it dx, the sums and the slabs in `ws`: (dx, partials, maxes,
+    True); outside that kernel's form NOTHING is computed and (None, None, None, False) comes back -- the caller then runs the
+    weight gradient, which writes the true dy through, and calls again with that."""
+    if mid is not None:
+        res = mid_bwd_fused(dy, mid[0], bsum[0], mid[1], mid[2], wb, bsum[1], bsum[2], bsum[3], bsum[4], bsum[5], bsum[6], mid[3], cfg, mid[4]) \
+            if bsum is not None and mid_bwd_eligible(dy, bsum[0], ks) else None
+        return res + (True,) if res is not None else (None, None, None, False)
     if head is not None and bsum is not None and head_bwd_eligible(dy, bsum[0], ks):
         res = head_bwd_fused(dy, dyb, bsum[0], head[0], head[1], wb, bsum[1], bsum[2], bsum[3], bsum[4], bsum[5], bsum[6], head[2], cfg, head[3])
         if res is not None:
@@ -722,6 +731,53 @@ def head_bwd_fused(dz: torch.Tensor, dzb, y: torch.Tensor, xf: torch.Tensor, xb,
     if rc == ENOFORM:
         return None
     _lib.check(rc, "uaps_head_bwd_fused")
+    return g, partials, maxes
+
+
+# the backward of a ConvBlock's second convolution at the 256-wide level and the BatchNorm-backward sums of the layer in front as one
+# full-width-row pass (csrc/mid_bwd_row.hip)
+_FUSED_MID = config.flag("UAPS_FUSED_MID_BWD", True)
+MID_BWD_KERNEL = "mid_bwd_row_kernel"
+
+
+def mid_bwd_eligible(dz: torch.Tensor, y: torch.Tensor, ks: int) -> bool:
+    """May mid_bwd_fused run for the gradient `dz` (its BatchNorm transform pending) and the raw conv output `y` in front (the
+    library checks the rest and answers ENOFORM)?"""
+    return (_FUSED_MID and ks == 3 and y.shape[1] == 16 and dz.shape[1] == 16 and y.shape[3] == 256 and y.shape[2] % 16 == 0
+            and get_mode() == "h16")
+
+
+def mid_bwd_fused(dz: torch.Tensor, lz, y: torch.Tensor, xf: torch.Tensor, xb, wb: torch.Tensor, mean, invstd, gamma, beta,
+                  slope: float, groups: int, want_bias: bool, cfg: int, ws: torch.Tensor):
+    """uaps_mid_bwd_fused: (g, partials, maxes) with the weight-gradient slabs written to `ws` (follow with _wrw_reduce and
+    lazybn.prepare_from_partials), or None -- nothing launched, nothing written -- where the call is outside the kernel's form.
+    lz (lazybn.Lazy, or None) is the pending transform of `dz`: the true gradient is formed on the way, bounded by lz.bound, and is
+    not written."""
+    B, Cout, H, W = dz.shape
+    Cin = y.shape[1]
+    dev = y.device
+    g = torch.empty_like(y)
+    partials = torch.empty((Cin, B, max(H // 16, 1), 2), dtype=torch.float32, device=dev)
+    maxes = torch.empty(2 * bounds.FLOATS, dtype=torch.float32, device=dev)
+    dzb = lz.bound if lz is not None else None
+    L = _lib.lib()
+    on = KERNEL_EVENTS is not None and (EVENT_FILTER is None or MID_BWD_KERNEL in EVENT_FILTER)
+    with _lib.device_guard(dev):
+        st = _lib.current_stream(dev)
+        _lib.check(L.uaps_zero_bounds(maxes.data_ptr(), maxes.numel(), st), "uaps_zero_bounds")
+        with (_lib.LaunchTimer() if on else contextlib.nullcontext()) as timer:
+            rc = L.uaps_mid_bwd_fused(dz.data_ptr(), lz.y.data_ptr() if lz is not None else None, lz.coef.data_ptr() if lz is not None else None,
+                                      float(lz.slope) if lz is not None else 0.0, int(lz.groups) if lz is not None else 1,
+                                      y.data_ptr(), xf.data_ptr(), float(slope), int(groups), wb.data_ptr(),
+                                      dzb[0].data_ptr() if dzb is not None else None, float(dzb[1]) if dzb is not None else 1.0,
+                                      xb[0].data_ptr() if xb is not None else None, float(xb[1]) if xb is not None else 1.0,
+                                      mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), int(want_bias), B, Cin, Cout,
+                                      H, W, 3, cfg, g.data_ptr(), partials.data_ptr(), maxes.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        if on and rc == 0:                            # both contractions: the weight gradient and the input gradient
+            KERNEL_EVENTS.setdefault(MID_BWD_KERNEL, []).append((timer.start, timer.stop, 2 * 2.0 * B * H * W * Cin * Cout * 9))
+    if rc == ENOFORM:
+        return None
+    _lib.check(rc, "uaps_mid_bwd_fused")
     return g, partials, maxes
 
 

@@ -342,14 +342,27 @@ class _BnActConv(torch.autograd.Function):
             return bounds.put(out, *lz.bound) if lz is not None else dz
 
         done_w = False
-        if lz_in is not None:
+        lazy_up = ctx.lazy_up and not lazybn.observed(y)      # (a hook / retain_grad registered on y since the forward gets the true gradient)
+        da = partials = maxes = None
+        if lz_in is not None and lazy_up and xb is not None and ctx.needs_input_grad[12] and _conv.mid_bwd_eligible(dz, y, ks):
+            # conv2 of a ConvBlock at the 256-wide level: weight-gradient slabs, input gradient AND this BatchNorm's backward sums from ONE
+            # pass over (d(activation), z, y); the true dz is never written (csrc/mid_bwd_row.hip).  res[3] False: outside that kernel's form,
+            # nothing was computed and the separate launches run below
+            res = _conv.conv_bwd_data_raw(dz, wb, Cc, ks, cfg, dyb=lz_in.bound, bsum=(y, stats[0], stats[1], gamma, beta, slope, groups),
+                                          mid=(lz_in, xf, xb, want_db, cws))
+            if res[3]:
+                da, partials, maxes = res[:3]
+                with _lib.device_guard(dev):
+                    _conv._wrw_reduce(cws, dw, db, B, Cc, Cout, H, W, ks, cfg, _lib.current_stream(dev), ctx.prefs, ctx.step)
+                done_w = True
+        if lz_in is not None and da is None:
             out = weight_gradient(dz, lz_in.bound, lz_in) if xb is not None else None
             done_w = out is not None
             dz = out if done_w else lazybn.materialize(dz, lz_in)
             dzb = bounds.get(dz)
-        lazy_up = ctx.lazy_up and not lazybn.observed(y)      # (a hook / retain_grad registered on y since the forward gets the true gradient)
-        partials = maxes = None
-        if lazy_up:      # where the input-gradient kernel can, its epilogue forms this BatchNorm's backward sums (no pass of their own)
+        if da is not None:
+            pass
+        elif lazy_up:    # where the input-gradient kernel can, its epilogue forms this BatchNorm's backward sums (no pass of their own)
             # out_conv at the 256-wide level: input gradient, this BatchNorm's backward sums AND the weight-gradient slabs from ONE pass
             # over (d logits, y) (csrc/head_bwd_row.hip); res[3] False: outside that kernel's form, the weight gradient runs below
             head = (xf, xb, want_db, cws) if (not done_w and ctx.needs_input_grad[12]) else None

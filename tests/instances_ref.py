@@ -153,6 +153,35 @@ def decode(pairs, H, W):
     return flat.reshape(H, W, order="F")
 
 
+def encode_batch(mask, classes):
+    """mask [B,H,W], any int64 class values -> (col_offsets int32 [B * n * W + 1], pairs int32 [total,2]) in the layout of
+    uaps_rle_count / uaps_rle_encode: segment j = b * n + c; a run belongs to the column its start lies in."""
+    B, H, W = mask.shape
+    per_col, pairs = [], []
+    for b in range(B):
+        for c in classes:
+            p = mask2rle_pairs(mask[b] == c)
+            pairs.append(p)
+            per_col.append(np.bincount((p[:, 0] - 1) // H, minlength=W))
+    per_col = np.concatenate(per_col)
+    col_offsets = np.concatenate([[0], np.cumsum(per_col)]).astype(np.int32)
+    return col_offsets, np.concatenate(pairs).astype(np.int32).reshape(-1, 2)
+
+
+def decode_batch(pairs, offsets, B, H, W, classes, dtype=np.int64):
+    """The plane-restricted decode of segments j = b * n + c, classes in order (later classes win): [B,H,W] of `dtype`.  Runs may be
+    unordered, overlap, and leave the plane on either side; what leaves it is dropped."""
+    out = np.zeros((B, H * W), dtype=dtype)
+    for b in range(B):
+        for k, c in enumerate(classes):
+            j = b * len(classes) + k
+            for s, n in pairs[offsets[j]:offsets[j + 1]]:
+                lo, hi = max(int(s) - 1, 0), min(int(s) - 1 + int(n), H * W)
+                if lo < hi:
+                    out[b, lo:hi] = c
+    return np.stack([f.reshape(H, W, order="F") for f in out])
+
+
 @functools.lru_cache(maxsize=None)
 def class_mask(B, H, W, C=3, seed=3):
     """Blobby label array with classes 0..C: long vertical and horizontal runs, runs through the column ends."""

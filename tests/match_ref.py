@@ -22,7 +22,7 @@ def match_image(lp, lg, np_all, ng_all, tp, tg, num_classes, thr=0.5, agnostic=F
     """One image.  lp, lg: label maps; np_all, ng_all: the true component counts; tp [Mp,9], tg [Mg,9]: the tables.
     -> pred int64 [Mp,4], target int64 [Mg,4], counts int64 [C,3], valid."""
     Mp, Mg = tp.shape[0], tg.shape[0]
-    n_p, n_g = min(int(np_all), Mp), min(int(ng_all), Mg)
+    n_p, n_g = max(0, min(int(np_all), Mp)), max(0, min(int(ng_all), Mg))      # (a negative count: no rows)
     inter = np.zeros((n_p + 1, n_g + 1), dtype=np.int64)
     for p in range(1, n_p + 1):
         y0, x0, y1, x1 = (int(v) for v in tp[p - 1, 2:6])       # the component's box: no pixel of p lies outside it

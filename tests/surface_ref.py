@@ -40,10 +40,10 @@ def tol_d2(tolerance):
     return None if tolerance is None else int(math.floor(float(tolerance) * float(tolerance)))
 
 
-def table(pred, target, C, percentile=95.0, tolerance=None):
-    """int64 [B,C,12] with Python-integer arithmetic."""
+def table(pred, target, C, percentile=95.0, tolerance=None, tol_sq=None):
+    """int64 [B,C,12] with Python-integer arithmetic.  tol_sq: the squared tolerance itself, in place of floor(tolerance^2)."""
     B = pred.shape[0]
-    t2 = tol_d2(tolerance)
+    t2 = tol_d2(tolerance) if tol_sq is None else int(tol_sq)
     out = np.zeros((B, C, 12), dtype=np.int64)
     for b in range(B):
         for c in range(C):

@@ -78,6 +78,13 @@ class Case(NamedTuple):
     offset: int = 0              # floats the logits (and dz) sit behind a 16-byte boundary: 1 = the misaligned scalar form
     seed: int = 0
 
+    @property
+    def kernels(self) -> frozenset:
+        """The instantiations uaps_binloss_fwd / _bwd launch for the case: SOFT = a float target; the four-element and the scalar
+        form are one kernel (`nvec` is an argument), so alignment and size change no name."""
+        soft = "true" if self.target == "float" else "false"
+        return frozenset({f"bin_fwd_kernel<{soft}>", "bin_finalize", f"bin_bwd_kernel<{soft}>"})
+
 
 # (1,5,7): 35 elements, the scalar tail alone.  (3,33,19): a count that is no multiple of 4.  (2,96,100): several blocks.
 # (3,512,512): 196608 groups of four, more than one pass of 512 blocks x 256 lanes (the kernels' block cap; tests/loss_ref.py has no
@@ -111,6 +118,14 @@ def cases():
             Case("3x512x512-int", (3, 512, 512), "int", pos_weight=3.0, seed=92),
             Case("3x512x512-float-g15", (3, 512, 512), "float", gamma=1.5, grad=0.25, seed=93)]
     return out
+
+
+CASES = cases()
+# the rest of csrc/loss_binary.hip has no case table: the sigmoid MSE / KL pair (test_sigmoid_mse_and_kl_vs_float64 launches all five)
+# and uaps_bin_confusion (test_bin_confusion_is_exact: the zeroing kernel and the counting one), none of them templated
+PAIR_KERNELS = frozenset({"sig_mse_fwd_kernel", "sig_mse_bwd_kernel", "sig_kl_fwd_kernel", "sig_kl_finalize", "sig_kl_bwd_kernel"})
+CONFUSION_KERNELS = frozenset({"zero4_kernel", "bin_confusion_kernel"})
+KERNEL_NAMES = ("bin_fwd_kernel", "bin_finalize", "bin_bwd_kernel", "bin_confusion_kernel", "zero4_kernel") + tuple(sorted(PAIR_KERNELS))
 
 
 def make_inputs(case: Case):

@@ -88,7 +88,7 @@ class Case:
     want_var: bool = True
     logit_scale: float = 1.0
     planted: str = ""            # "zero": pixels whose fp32 probabilities underflow to 0; "ties": exact two-class ties
-    bad_labels: bool = False     # labels of -1, C and 255 on a few pixels (the supervised half is then not compared, only finite)
+    bad_labels: bool = False     # labels of -1, C, 255 and five values no int holds on a few pixels (the supervised half is then not compared, only finite)
     seed_id: str = ""            # cases that must agree bit for bit share their data: seeded from this instead of the id
 
     @property
@@ -244,8 +244,8 @@ def inputs(case: Case) -> dict:
         pix = np.nonzero(close)[0]
         put(un, pix, (rng.standard_normal((D, pix.size, C)) * sc).astype(np.float32))
     if case.bad_labels:
-        pix = rng.choice(N, size=min(N, 9), replace=False)
-        labels.reshape(-1)[pix] = np.resize(np.array([-1, C, 255], np.int64), pix.size)
+        pix = rng.choice(N, size=min(N, 16), replace=False)     # the last five fit no int: narrowed, three of them would be classes 1, 1, 0
+        labels.reshape(-1)[pix] = np.resize(np.array([-1, C, 255, 2 ** 31, 2 ** 32 + 1, -2 ** 32 + 1, -2 ** 63, 2 ** 63 - 1], np.int64), pix.size)
         d["n_bad"] = int(pix.size)
     return d
 

@@ -48,12 +48,16 @@ template <int VEC> __device__ __forceinline__ void store_vec(float* p, const flo
     if constexpr (VEC == 4) { v.x = in[0]; v.y = in[1]; v.z = in[2]; v.w = in[3]; }
     *reinterpret_cast<V*>(p) = v;
 }
+// An int64 label as the int the kernels test against [0, C): decided in 64 bits, so a value an int cannot hold (2^32 + 1 would narrow to
+// class 1, INT64_MIN to class 0) becomes -1 = outside, counted and in no term.  A zero high word leaves the low word as it is: from
+// 2^31 on it reads as a negative int, outside as well.  One 32-bit compare and select per label.
+__device__ __forceinline__ int narrow_label(long long t) { return (int)(t >> 32) != 0 ? -1 : (int)t; }
 template <int VEC> __device__ __forceinline__ void load_labels(const int64_t* p, int (&out)[VEC]) {
-    if constexpr (VEC == 1) { out[0] = (int)p[0]; }
-    if constexpr (VEC == 2) { longlong2 v = *reinterpret_cast<const longlong2*>(p); out[0] = (int)v.x; out[1] = (int)v.y; }
+    if constexpr (VEC == 1) { out[0] = narrow_label(p[0]); }
+    if constexpr (VEC == 2) { longlong2 v = *reinterpret_cast<const longlong2*>(p); out[0] = narrow_label(v.x); out[1] = narrow_label(v.y); }
     if constexpr (VEC == 4) {
         longlong2 a = *reinterpret_cast<const longlong2*>(p), b = *reinterpret_cast<const longlong2*>(p + 2);
-        out[0] = (int)a.x; out[1] = (int)a.y; out[2] = (int)b.x; out[3] = (int)b.y;
+        out[0] = narrow_label(a.x); out[1] = narrow_label(a.y); out[2] = narrow_label(b.x); out[3] = narrow_label(b.y);
     }
 }
 template <int VEC> __device__ __forceinline__ void store_labels(int64_t* p, const int (&in)[VEC]) {

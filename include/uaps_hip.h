@@ -1534,7 +1534,8 @@ int uaps_match_instances(const uaps_match_call* call);
  *              (int32 [B, max_regions, bins] in the workspace; only the rows below min(count[b], max_regions) are zeroed and used, the
  *              bound is read on the device).  Then pro_sum float64 [B, n_classes, bins]: pro_sum[b, k, i] = the sum over the regions r of
  *              image b whose class is classes[k], in ascending r, of (double) suffix_r(i) / (double) area_r, suffix_r(i) = sum over
- *              j >= i of region_hist[b, r, j], area_r = table[b, r, 1]; n_regions int64 [B, n_classes] their number.
+ *              j >= i of region_hist[b, r, j], area_r = table[b, r, 1]; n_regions int64 [B, n_classes] their number.  A row whose
+ *              area is not positive is no region: it is not counted and adds nothing.
  *   Launches: zero; one pass over the scores (four pixels a lane with 16-byte loads where H * W % 4 == 0 and the tensors are 16-byte
  *   aligned, rows privatised in at most 64 KB of LDS as 32-bit counters, lanes of a wave with one key counted by ballot, non-zero words
  *   flushed with 64-bit integer atomics; rows that do not fit are processed in groups along the grid's second dimension); with regions

@@ -124,12 +124,13 @@ def histograms(rows, bins, lo, hi, want_sums):
     return hist, qsum, nan
 
 
-def curves(S, t, classes=None, bins=1024, top=True, from_logits=False, regions=None, want_sums=False):
-    """dict(hist, qsum, nan, pro_sum, n_regions, valid) of uaps_score_curves; regions = (labels, count, table) of label_batch."""
+def curves(S, t, classes=None, bins=1024, top=True, from_logits=False, regions=None, want_sums=False, lo=0.0, hi=1.0):
+    """dict(hist, qsum, nan, pro_sum, n_regions, valid) of uaps_score_curves; regions = (labels, count, table) of label_batch.  A table
+    row whose area is not positive is no region: it is not counted and adds nothing."""
     S, t = np.asarray(S, dtype=F32), np.asarray(t).astype(np.int64)
     B, C = S.shape[:2]
     classes = ([1] if C == 1 else list(range(1, C))) if classes is None else list(classes)
-    hist, qsum, nan = histograms(rows_of(S, t, classes, top, from_logits), bins, 0.0, 1.0, want_sums)
+    hist, qsum, nan = histograms(rows_of(S, t, classes, top, from_logits), bins, lo, hi, want_sums)
     out = dict(hist=hist, qsum=qsum, nan=nan, pro_sum=None, n_regions=None, valid=np.ones(B, dtype=bool))
     if regions is None:
         return out
@@ -145,14 +146,14 @@ def curves(S, t, classes=None, bins=1024, top=True, from_logits=False, regions=N
             h = np.zeros(bins, dtype=np.int64)
             if plane is not None:
                 s = P[b, plane][labels[b] == r + 1]
-                h = np.bincount(bins_of(s[~np.isnan(s)], bins), minlength=bins)
+                h = np.bincount(bins_of(s[~np.isnan(s)], bins, lo, hi), minlength=bins)
             suffix = np.zeros(bins, dtype=np.int64)
             run = 0
             for i in range(bins - 1, -1, -1):
                 run += int(h[i])
                 suffix[i] = run
             for k, ck in enumerate(classes):
-                if ck == c:
+                if ck == c and area > 0:
                     n_reg[b, k] += 1
                     pro[b, k] += suffix.astype(np.float64) / np.float64(area)
     out.update(pro_sum=pro, n_regions=n_reg, valid=np.asarray(count) <= Mg)
@@ -165,8 +166,8 @@ def plane(score, pred, target, bins=1024, lo=0.0, hi=1.0, want_sums=False):
     return dict(hist=hist, qsum=qsum, nan=nan, pro_sum=None, n_regions=None, valid=np.ones(score.shape[0], dtype=bool))
 
 
-def assert_result(res, ref, what="", pro_rel=1e-12):
-    """Every integer output exactly, pro_sum to a relative 1e-12."""
+def assert_result(res, ref, what="", pro_rel=0.0):
+    """Every integer output exactly, and pro_sum bit for bit: both sides add IEEE double quotients in ascending region order."""
     for name in ("hist", "qsum", "nan", "n_regions"):
         got, want = getattr(res, name), ref[name]
         assert (got is None) == (want is None), (what, name)

@@ -1,5 +1,5 @@
 """Threshold-sweep histograms on the GPU (csrc/curves.hip) against the brute-force reference (tests/curves_ref.py) and against the
-module's CPU path.  Every integer output is compared exactly, pro_sum to a relative 1e-12.
+module's CPU path.  Every integer output is compared exactly, pro_sum bit for bit.
 
 The histogram kernel gives a lane four consecutive pixels (16-byte loads) where H * W is a multiple of four -- 7 x 300, 130 x 70,
 256 x 256 -- and one pixel otherwise -- 1 x 1, 1 x 45, 37 x 53; a workgroup walks 1024 or 4096 pixels of one image, so 256 x 256 spans

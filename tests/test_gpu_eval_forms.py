@@ -51,7 +51,7 @@ from test_gpu_ops_forms import DEV, EINVAL, ERANGE, EWORKSPACE, OK, Buf, _stream
 
 pytestmark = pytest.mark.gpu
 GUARD = 64                                    # sentinel elements in front of and behind every view
-SENT = {torch.float32: -12345.0, torch.uint8: 0xA5, torch.int64: -7, torch.int32: -77777}
+SENT = {torch.float32: -12345.0, torch.uint8: 0xA5, torch.int64: -7, torch.int32: -77777, torch.float64: -12345.0}
 OUT_FILL, WS_FILL = 0xEE, 0x7F
 TORCH_OF = {E.U8: torch.uint8, E.I32: torch.int32, E.I64: torch.int64}
 

@@ -1013,6 +1013,28 @@ int uaps_mid_bwd_fused(const float* dact, const float* y2, const float* coef, fl
                        const float* beta, int want_bias, int B, int Cin, int Cout, int H, int W, int ks, int cfg, float* g,
                        void* partials, float* maxes, void* workspace, size_t workspace_bytes, uaps_stream_t stream);
 
+/* The input gradient of up4's first convolution with the fold of its up-sampled half as ONE pass (csrc/up_bwd_row.hip) where
+ * uaps_conv_bwd_data_cat and uaps_up_cat_bwd(dx2, NULL, dlow, B, 0, C2, H / 2, W / 2) ran one after the other: dy [B,Cout,H,W] is the
+ * gradient of conv(cat([skip, up2x(low)]), w), wb the packed input-gradient weights of w, dy_bound (times dy_mul) bounds |dy| as
+ * uaps_call_hints::bound[0] of uaps_conv_bwd_data_cat.  Written: dskip [B,C1,H,W], bit-identical to that call's dx1, and dlow
+ * [B,C2,H/2,W/2], equal to the two calls' result for finite gradients up to the sign of a zero (the fold leaves out the candidates of
+ * weight 0); the full-resolution gradient of the up-sampled tensor is not written.  A non-finite gradient raises
+ * UAPS_ERR_CONV_NONFINITE in the error word.  Only enqueues on `stream`; no float atomics, two launches give the same bits.
+ * One form: ks == 3, Cout == C1 == C2 == 16, W == 256, H % 16 == 0, mode 2 (fp16-split arithmetic) with the bound present, 16-byte
+ * aligned tensors, cfg 0 (UAPS_CONV_BOUNDED ignored), the full-width-row kernels not tuned off, and a size for which
+ * uaps_up_bwd_fused_form answers UAPS_OK.  Anything else returns UAPS_ENOFORM with nothing launched: make the two separate calls. */
+int uaps_up_bwd_fused(const float* dy, const float* wb, const float* dy_bound, float dy_mul, float* dskip, int C1, float* dlow, int C2,
+                      int B, int Cout, int H, int W, int ks, int cfg, uaps_stream_t stream);
+/* Host only.  The float32 index rule of the x2 align_corners interpolation from n_in to 2 n_in samples (src = mul_rn(r, o),
+ * i0 = (int)src, i1 = i0 + (i0 < n_in - 1), weights 1 - frac and frac): the smallest and largest o - 2 i over every pair (output
+ * index o, input index i) of non-zero weight.  (-1, 2) is the four-tap support 2 i - 1 .. 2 i + 2 that uaps_up_bwd_fused needs. */
+int uaps_up_fold_support(int n_in, int* min_offset, int* max_offset);
+/* Host only.  UAPS_OK where the size (H, W) of dy is inside uaps_up_bwd_fused's form (W == 256, H % 16 == 0, four-tap support along
+ * both axes), else UAPS_ENOFORM. */
+int uaps_up_bwd_fused_form(int H, int W);
+/* Host only.  The number of workgroups uaps_up_bwd_fused launches for B images of H rows (each walks its share of the B * H / 16 runs). */
+int uaps_up_bwd_fused_grid(int B, int H);
+
 /* The same when the join's output had k <= 4 consumers: dx = (dout[0] + ... + dout[k-1]) * (out > 0), the k gradients (host
  * array of device pointers) summed in order by this pass instead of by k - 1 accumulation passes in front of it. */
 int uaps_relu_bwd_sum(const float* const* dout_host, int k, const float* out, float* dx, long n, uaps_stream_t stream);

@@ -130,6 +130,10 @@ SIGNATURES = {
                             [_PTR] * 4 + [C.c_size_t, _PTR]),
     "uaps_mid_bwd_fused": (C.c_int, [_PTR] * 3 + [C.c_float, C.c_int, _PTR, _PTR, C.c_float, C.c_int, _PTR, _PTR, C.c_float, _PTR, C.c_float] +
                            [_PTR] * 4 + [C.c_int] * 8 + [_PTR] * 4 + [C.c_size_t, _PTR]),
+    "uaps_up_bwd_fused": (C.c_int, [_PTR, _PTR, _PTR, C.c_float, _PTR, C.c_int, _PTR] + [C.c_int] * 7 + [_PTR]),
+    "uaps_up_fold_support": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "uaps_up_bwd_fused_form": (C.c_int, [C.c_int, C.c_int]),
+    "uaps_up_bwd_fused_grid": (C.c_int, [C.c_int, C.c_int]),
     "uaps_seg_confusion": (C.c_int, [_PTR, _PTR] + [C.c_int] * 4 + [_PTR, _PTR]),
     "uaps_ema_update": (C.c_int, [_PTR] * 3 + [C.c_int, C.c_float, C.c_float, _PTR]),
     "uaps_teacher_noise": (C.c_int, [_PTR] + [C.c_int] * 5 + [C.c_uint64, C.c_uint64, _PTR, _PTR]),

@@ -27,6 +27,7 @@ DOC = {
     "UAPS_FUSED_BN_SUMS": "BatchNorm-backward sums in the epilogue of the 16 -> 16 input-gradient row kernel (measured a wash: off)",
     "UAPS_FUSED_HEAD_BWD": "out_conv's input gradient, weight gradient and the BatchNorm-backward sums behind it as one row pass (csrc/head_bwd_row.hip)",
     "UAPS_FUSED_MID_BWD": "the 16 -> 16 convolution of a 256-wide ConvBlock: weight gradient, input gradient and the BatchNorm-backward sums behind it as one row pass (csrc/mid_bwd_row.hip)",
+    "UAPS_FUSED_UP_FOLD": "the input gradient of up4's first convolution folds its up-sampled half to the low resolution inside the row kernel (csrc/up_bwd_row.hip)",
     "UAPS_LAZY_BN_BWD": "BatchNorm backward in two halves on the 256-wide decoder layers (lazybn)",
     "UAPS_PAIR_CFG": "cfg bits of the pair-loss kernels (diagnosis)",
     "UAPS_FUSED_FANOUT": "all perturbed copies of a feature map written by one pass over it",

@@ -781,6 +781,42 @@ def mid_bwd_fused(dz: torch.Tensor, lz, y: torch.Tensor, xf: torch.Tensor, xb, w
     return g, partials, maxes
 
 
+# the input gradient of up4's first convolution with the fold of its up-sampled half as one full-width-row pass (csrc/up_bwd_row.hip)
+_FUSED_UP_FOLD = config.flag("UAPS_FUSED_UP_FOLD", True)
+UP_BWD_KERNEL = "up_bwd_row_kernel"
+
+
+def up_bwd_eligible(dy: torch.Tensor, C1: int, C2: int, ks: int) -> bool:
+    """May up_bwd_fused run for the gradient `dy` of a convolution of cat([skip (C1 channels), up2x(low) (C2 channels)]) (the library
+    checks the rest and answers ENOFORM)?"""
+    return (_FUSED_UP_FOLD and ks == 3 and dy.shape[1] == 16 and C1 == 16 and C2 == 16 and dy.shape[3] == 256 and dy.shape[2] % 16 == 0
+            and get_mode() == "h16")
+
+
+def up_bwd_fused(dy: torch.Tensor, dyb, wb: torch.Tensor, C1: int, C2: int, cfg: int):
+    """uaps_up_bwd_fused: (d(skip), d(low)), or None -- nothing launched, nothing written -- where the call is outside the kernel's
+    form.  The full-resolution gradient of the up-sampled tensor is not written."""
+    B, Cout, H, W = dy.shape
+    dev = dy.device
+    if dyb is None:
+        return None
+    dskip = torch.empty((B, C1, H, W), dtype=torch.float32, device=dev)
+    dlow = torch.empty((B, C2, H // 2, W // 2), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    on = KERNEL_EVENTS is not None and (EVENT_FILTER is None or UP_BWD_KERNEL in EVENT_FILTER)
+    with _lib.device_guard(dev):
+        st = _lib.current_stream(dev)
+        with (_lib.LaunchTimer() if on else contextlib.nullcontext()) as timer:
+            rc = L.uaps_up_bwd_fused(dy.data_ptr(), wb.data_ptr(), dyb[0].data_ptr(), float(dyb[1]), dskip.data_ptr(), C1, dlow.data_ptr(), C2,
+                                     B, Cout, H, W, 3, cfg, st)
+        if on and rc == 0:
+            KERNEL_EVENTS.setdefault(UP_BWD_KERNEL, []).append((timer.start, timer.stop, 2.0 * B * H * W * (C1 + C2) * Cout * 9))
+    if rc == ENOFORM:
+        return None
+    _lib.check(rc, "uaps_up_bwd_fused")
+    return dskip, dlow
+
+
 def conv_bwd_weight_raw(dy: torch.Tensor, x: torch.Tensor, ks: int, want_bias: bool, cfg: int = 0, wkey=None, bkey=None,
                         dyb=None, xb=None, lz=None, prefs=None, step=None):
     """wkey / bkey: id() of the weight / bias parameter, for a registered gradient destination (_graddest).
@@ -1012,7 +1048,12 @@ class _Conv2dCat(torch.autograd.Function):
                 else:
                     dy = lazybn.materialize(dy, lz)
                 dyb = bounds.get(dy)
-            if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            folded = None
+            if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and up2 and up_bwd_eligible(dy, C1, C2, ks):
+                folded = up_bwd_fused(dy, dyb, wb, C1, C2, cfg)
+            if folded is not None:
+                dx1, dx2 = folded
+            elif ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
                 dx1 = torch.empty_like(x1)
                 dx2 = torch.empty((B, C2, H, W), dtype=torch.float32, device=dev) if up2 else torch.empty_like(x2)
                 hh = _lib.mk_hints((dyb,)) if dyb is not None else None
@@ -1022,7 +1063,7 @@ class _Conv2dCat(torch.autograd.Function):
                 _lib.check(rc, "uaps_conv_bwd_data_cat")
             if want_w and not done_w:
                 dw, db, _ = weight_gradient(dy, dyb, None)
-            if up2 and dx2 is not None:               # the gradient of the up-sampled tensor folds to the low-resolution one (uaps_up_cat_bwd)
+            if up2 and dx2 is not None and folded is None:      # the gradient of the up-sampled tensor folds to the low-resolution one (uaps_up_cat_bwd)
                 dlow = torch.empty_like(x2)
                 rc = L.uaps_up_cat_bwd(dx2.data_ptr(), None, dlow.data_ptr(), B, 0, C2, H // 2, W // 2, st)
                 _lib.check(rc, "uaps_up_cat_bwd")

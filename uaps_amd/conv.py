@@ -9,7 +9,6 @@ fallback on this path: CPU tensors are refused.
 from __future__ import annotations
 
 import collections
-import contextlib
 import ctypes as C
 import os
 import weakref
@@ -125,6 +124,34 @@ class _timed:
             self.t.__exit__()
             KERNEL_EVENTS.setdefault(self.name, []).append((self.t.start, self.t.stop, self.flops))
         return False
+
+
+class _fused_pass:
+    """One launch of a fused row pass `entry` (csrc/*_bwd_row.hip): while KERNEL_EVENTS collects, times it under the kernel's name;
+    the body stores the entry point's return code in `rc`.  launched() is the tail: False -- nothing launched, nothing written --
+    where the call is outside the kernel's form, an exception for any other failure."""
+
+    def __init__(self, entry: str, kernel: str, flops: float):
+        self.entry, self.kernel, self.flops, self.rc = entry, kernel, flops, ENOFORM
+        self.on = KERNEL_EVENTS is not None and (EVENT_FILTER is None or kernel in EVENT_FILTER)
+
+    def __enter__(self):
+        if self.on:
+            self.t = _lib.LaunchTimer().__enter__()
+        return self
+
+    def __exit__(self, *a):
+        if self.on:
+            self.t.__exit__()
+            if self.rc == 0:
+                KERNEL_EVENTS.setdefault(self.kernel, []).append((self.t.start, self.t.stop, self.flops))
+        return False
+
+    def launched(self) -> bool:
+        if self.rc == ENOFORM:
+            return False
+        _lib.check(self.rc, self.entry)
+        return True
 
 
 def set_mode(mode) -> None:
@@ -716,22 +743,17 @@ def head_bwd_fused(dz: torch.Tensor, dzb, y: torch.Tensor, xf: torch.Tensor, xb,
     partials = torch.empty((Cin, B, max(H // 16, 1), 2), dtype=torch.float32, device=dev)
     maxes = torch.empty(2 * bounds.FLOATS, dtype=torch.float32, device=dev)
     L = _lib.lib()
-    on = KERNEL_EVENTS is not None and (EVENT_FILTER is None or HEAD_BWD_KERNEL in EVENT_FILTER)
     with _lib.device_guard(dev):
         st = _lib.current_stream(dev)
         _lib.check(L.uaps_zero_bounds(maxes.data_ptr(), maxes.numel(), st), "uaps_zero_bounds")
-        with (_lib.LaunchTimer() if on else contextlib.nullcontext()) as timer:
-            rc = L.uaps_head_bwd_fused(dz.data_ptr(), y.data_ptr(), xf.data_ptr(), float(slope), int(groups), wb.data_ptr(),
-                                       dzb[0].data_ptr() if dzb is not None else None, float(dzb[1]) if dzb is not None else 1.0,
-                                       xb[0].data_ptr() if xb is not None else None, float(xb[1]) if xb is not None else 1.0,
-                                       mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), int(want_bias), B, Cin, Cout,
-                                       H, W, 3, cfg, g.data_ptr(), partials.data_ptr(), maxes.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        if on and rc == 0:                            # both contractions: the weight gradient and the input gradient
-            KERNEL_EVENTS.setdefault(HEAD_BWD_KERNEL, []).append((timer.start, timer.stop, 2 * 2.0 * B * H * W * Cin * Cout * 9))
-    if rc == ENOFORM:
-        return None
-    _lib.check(rc, "uaps_head_bwd_fused")
-    return g, partials, maxes
+        # (the flops of both contractions: the weight gradient and the input gradient)
+        with _fused_pass("uaps_head_bwd_fused", HEAD_BWD_KERNEL, 2 * 2.0 * B * H * W * Cin * Cout * 9) as p:
+            p.rc = L.uaps_head_bwd_fused(dz.data_ptr(), y.data_ptr(), xf.data_ptr(), float(slope), int(groups), wb.data_ptr(),
+                                         dzb[0].data_ptr() if dzb is not None else None, float(dzb[1]) if dzb is not None else 1.0,
+                                         xb[0].data_ptr() if xb is not None else None, float(xb[1]) if xb is not None else 1.0,
+                                         mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), int(want_bias), B, Cin, Cout,
+                                         H, W, 3, cfg, g.data_ptr(), partials.data_ptr(), maxes.data_ptr(), ws.data_ptr(), ws.numel(), st)
+    return (g, partials, maxes) if p.launched() else None
 
 
 # the backward of a ConvBlock's second convolution at the 256-wide level and the BatchNorm-backward sums of the layer in front as one
@@ -761,24 +783,19 @@ def mid_bwd_fused(dz: torch.Tensor, lz, y: torch.Tensor, xf: torch.Tensor, xb, w
     maxes = torch.empty(2 * bounds.FLOATS, dtype=torch.float32, device=dev)
     dzb = lz.bound if lz is not None else None
     L = _lib.lib()
-    on = KERNEL_EVENTS is not None and (EVENT_FILTER is None or MID_BWD_KERNEL in EVENT_FILTER)
     with _lib.device_guard(dev):
         st = _lib.current_stream(dev)
         _lib.check(L.uaps_zero_bounds(maxes.data_ptr(), maxes.numel(), st), "uaps_zero_bounds")
-        with (_lib.LaunchTimer() if on else contextlib.nullcontext()) as timer:
-            rc = L.uaps_mid_bwd_fused(dz.data_ptr(), lz.y.data_ptr() if lz is not None else None, lz.coef.data_ptr() if lz is not None else None,
-                                      float(lz.slope) if lz is not None else 0.0, int(lz.groups) if lz is not None else 1,
-                                      y.data_ptr(), xf.data_ptr(), float(slope), int(groups), wb.data_ptr(),
-                                      dzb[0].data_ptr() if dzb is not None else None, float(dzb[1]) if dzb is not None else 1.0,
-                                      xb[0].data_ptr() if xb is not None else None, float(xb[1]) if xb is not None else 1.0,
-                                      mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), int(want_bias), B, Cin, Cout,
-                                      H, W, 3, cfg, g.data_ptr(), partials.data_ptr(), maxes.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        if on and rc == 0:                            # both contractions: the weight gradient and the input gradient
-            KERNEL_EVENTS.setdefault(MID_BWD_KERNEL, []).append((timer.start, timer.stop, 2 * 2.0 * B * H * W * Cin * Cout * 9))
-    if rc == ENOFORM:
-        return None
-    _lib.check(rc, "uaps_mid_bwd_fused")
-    return g, partials, maxes
+        # (the flops of both contractions: the weight gradient and the input gradient)
+        with _fused_pass("uaps_mid_bwd_fused", MID_BWD_KERNEL, 2 * 2.0 * B * H * W * Cin * Cout * 9) as p:
+            p.rc = L.uaps_mid_bwd_fused(dz.data_ptr(), lz.y.data_ptr() if lz is not None else None, lz.coef.data_ptr() if lz is not None else None,
+                                        float(lz.slope) if lz is not None else 0.0, int(lz.groups) if lz is not None else 1,
+                                        y.data_ptr(), xf.data_ptr(), float(slope), int(groups), wb.data_ptr(),
+                                        dzb[0].data_ptr() if dzb is not None else None, float(dzb[1]) if dzb is not None else 1.0,
+                                        xb[0].data_ptr() if xb is not None else None, float(xb[1]) if xb is not None else 1.0,
+                                        mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), int(want_bias), B, Cin, Cout,
+                                        H, W, 3, cfg, g.data_ptr(), partials.data_ptr(), maxes.data_ptr(), ws.data_ptr(), ws.numel(), st)
+    return (g, partials, maxes) if p.launched() else None
 
 
 # the input gradient of up4's first convolution with the fold of its up-sampled half as one full-width-row pass (csrc/up_bwd_row.hip)
@@ -803,18 +820,10 @@ def up_bwd_fused(dy: torch.Tensor, dyb, wb: torch.Tensor, C1: int, C2: int, cfg:
     dskip = torch.empty((B, C1, H, W), dtype=torch.float32, device=dev)
     dlow = torch.empty((B, C2, H // 2, W // 2), dtype=torch.float32, device=dev)
     L = _lib.lib()
-    on = KERNEL_EVENTS is not None and (EVENT_FILTER is None or UP_BWD_KERNEL in EVENT_FILTER)
-    with _lib.device_guard(dev):
-        st = _lib.current_stream(dev)
-        with (_lib.LaunchTimer() if on else contextlib.nullcontext()) as timer:
-            rc = L.uaps_up_bwd_fused(dy.data_ptr(), wb.data_ptr(), dyb[0].data_ptr(), float(dyb[1]), dskip.data_ptr(), C1, dlow.data_ptr(), C2,
-                                     B, Cout, H, W, 3, cfg, st)
-        if on and rc == 0:
-            KERNEL_EVENTS.setdefault(UP_BWD_KERNEL, []).append((timer.start, timer.stop, 2.0 * B * H * W * (C1 + C2) * Cout * 9))
-    if rc == ENOFORM:
-        return None
-    _lib.check(rc, "uaps_up_bwd_fused")
-    return dskip, dlow
+    with _lib.device_guard(dev), _fused_pass("uaps_up_bwd_fused", UP_BWD_KERNEL, 2.0 * B * H * W * (C1 + C2) * Cout * 9) as p:
+        p.rc = L.uaps_up_bwd_fused(dy.data_ptr(), wb.data_ptr(), dyb[0].data_ptr(), float(dyb[1]), dskip.data_ptr(), C1, dlow.data_ptr(), C2,
+                                   B, Cout, H, W, 3, cfg, _lib.current_stream(dev))
+    return (dskip, dlow) if p.launched() else None
 
 
 def conv_bwd_weight_raw(dy: torch.Tensor, x: torch.Tensor, ks: int, want_bias: bool, cfg: int = 0, wkey=None, bkey=None,

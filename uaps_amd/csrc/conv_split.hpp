@@ -779,6 +779,15 @@ __host__ __device__ inline long pack_fwd_floats(const PackDesc& q) { return pack
 __host__ __device__ inline long pack_bwd_floats(const PackDesc& q) { return pack_nbk(q) + 3 * pack_nsb(q) + kH16Header + 2 * pack_nsb(q); }
 __host__ __device__ inline long pack_h16_fwd_off(const PackDesc& q) { return pack_nf(q) + 3 * pack_nsf(q); }      // the header; the pieces follow it
 __host__ __device__ inline long pack_h16_bwd_off(const PackDesc& q) { return pack_nbk(q) + 3 * pack_nsb(q); }
+// The fp16 pieces, their scale triple {s, 1 / s, max|w|} and the channel groups per tap inside the packed input-gradient weights `wb`
+// of a 3x3 convolution Cin -> Cout (Cout > 4: the contraction channels in chunks of 8)
+struct H16BwdWeights { const float* wp; const float* wscale; int CGP; };
+inline H16BwdWeights h16_bwd_weights(const float* wb, int Cin, int Cout) {
+    PackDesc q{};
+    q.taps = 9; q.CoutPk = (Cout + 7) / 8 * 8; q.CinPn = (Cin + 15) / 16 * 16; q.CGb = split_cgroups(Cout);
+    const float* hdr = wb + pack_h16_bwd_off(q);
+    return H16BwdWeights{hdr + kH16Header, hdr + kH16Parts, q.CGb};
+}
 
 __device__ __forceinline__ void conv_pack_elem(const PackDesc& q, long e) {
     const long nf = pack_nf(q), nbk = pack_nbk(q), ns = pack_nsf(q) + pack_nsb(q);

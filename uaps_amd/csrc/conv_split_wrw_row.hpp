@@ -15,6 +15,7 @@
 // enter the sums differs, so the results agree to rounding, not bit for bit.
 #pragma once
 #include "conv_split_wrw.hpp"
+#include "row_pieces.hpp"
 #include "up2_staging.hpp"
 
 namespace uaps {
@@ -34,8 +35,9 @@ namespace uaps {
 // of two low rows per channel into the registers of a plain wave's one full-row load.
 template <int WCI, bool XF, bool STRIP = false, bool DT = false, int DEPTH = 1, bool UP2 = false>
 __device__ __forceinline__ void conv_hrwrw_body(const ConvWrwArgs& a) {
-    constexpr int WIDTH = 256, NG = WIDTH / 8, XG = NG + 2, NSLOT = 3, ROWS = 16;
-    constexpr int CI = 16 * WCI, NWV = 4 * WCI, NTHR = 64 * NWV;
+    using G = RowGeom<16 * WCI>;                          // the geometry of the shared pieces (row_pieces.hpp: A, B and C run here)
+    constexpr int WIDTH = G::WIDTH, NG = G::NG, XG = G::XG, NSLOT = G::NSLOT, ROWS = G::ROWS;
+    constexpr int CI = G::CI, NWV = 4 * WCI, NTHR = 64 * NWV;
     constexpr int NXL = CI / NWV, NDL = 16 / NWV;        // input / dy channels a wave fetches per row: 4 and 4 (WCI 1) or 4 and 2 (WCI 2)
     constexpr int XCH = NSLOT * XG;                       // units per input channel
     constexpr int X_UNITS = 2 * CI * XCH, D_UNITS = 2 * 16 * NG;
@@ -224,8 +226,6 @@ __device__ __forceinline__ void conv_hrwrw_body(const ConvWrwArgs& a) {
     f32x4 accb = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < 9; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    constexpr unsigned kOnes = 0x3C003C00u;               // two fp16 1.0
-    const f16x8 ones = __builtin_bit_cast(f16x8, u32x4{kOnes, kOnes, kOnes, kOnes});
 
     for (int run = run_begin; run < run_end; ++run) {
         const int b = run / rpi, rr = run % rpi, r0 = (rr % rps) * ROWS;
@@ -270,42 +270,13 @@ __device__ __forceinline__ void conv_hrwrw_body(const ConvWrwArgs& a) {
         __syncthreads();
         int s0 = 0;                                       // slot of input row y - 1; rows y, y + 1 follow cyclically
         auto contract = [&]() {                           // dy row (sD) against the three live input rows
+            const auto slot_of = [&](int ky) { const int slot = s0 + ky; return slot >= NSLOT ? slot - NSLOT : slot; };
 #pragma unroll
             for (int sgi = 0; sgi < 2; ++sgi) {
                 const int gq = (sp * 2 + sgi) * 4 + kq;  // this lane's 8-pixel group of the row
                 f16x8 af[2];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) af[p] = __builtin_bit_cast(f16x8, sD[(p * 16 + j) * NG + gq]);
-                if (want_bias && wci == 0) {              // every dy element exactly once
-                    accb = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], ones, accb, 0, 0, 0);
-                    accb = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], ones, accb, 0, 0, 0);
-                }
-#pragma unroll
-                for (int ky = 0; ky < 3; ++ky) {
-                    int slot = s0 + ky; slot = slot >= NSLOT ? slot - NSLOT : slot;
-                    f16x8 bf[3][2];                        // [shift kx][piece]
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-                        const int u = ((p * CI + wci * 16 + j) * NSLOT + slot) * XG + gq + 1;
-                        const u32x4 c = sX[u];
-                        const unsigned cl3 = reinterpret_cast<const unsigned*>(&sX[u - 1])[3];      // pixels x - 2, x - 1 of the group's first pixel
-                        const unsigned cr0 = reinterpret_cast<const unsigned*>(&sX[u + 1])[0];      // pixels x + 8, x + 9
-                        const unsigned t01 = __builtin_amdgcn_alignbit(c[1], c[0], 16), t12 = __builtin_amdgcn_alignbit(c[2], c[1], 16);
-                        const unsigned t23 = __builtin_amdgcn_alignbit(c[3], c[2], 16);
-                        const unsigned tE0 = __builtin_amdgcn_alignbit(c[0], cl3, 16), t3E = __builtin_amdgcn_alignbit(cr0, c[3], 16);
-                        bf[0][p] = __builtin_bit_cast(f16x8, u32x4{tE0, t01, t12, t23});           // pixels x - 1
-                        bf[1][p] = __builtin_bit_cast(f16x8, c);
-                        bf[2][p] = __builtin_bit_cast(f16x8, u32x4{t01, t12, t23, t3E});           // pixels x + 1
-                    }
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        f32x4 c = acc[ky * 3 + kx];
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1], bf[kx][0], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bf[kx][1], c, 0, 0, 0);
-                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0], bf[kx][0], c, 0, 0, 0);
-                        acc[ky * 3 + kx] = c;
-                    }
-                }
+                read_dy_frag<G>(sD, j, gq, af);
+                tap_contract<G>(sX, af, wci * 16 + j, gq, slot_of, want_bias && wci == 0, acc, accb);      // (the bias: every dy element exactly once)
             }
         };
         if constexpr (DEPTH == 1) {
@@ -347,51 +318,9 @@ __device__ __forceinline__ void conv_hrwrw_body(const ConvWrwArgs& a) {
     }
 
     // ---- sum the four K-split partials of each input-channel block through LDS (fixed order), as conv_swrw_body ----
-    float* red = reinterpret_cast<float*>(sX);             // [slot][wci][10][4][64]; the staging image is dead (the loop ended with a barrier)
-#pragma unroll
-    for (int s = 2; s >= 1; s >>= 1) {
-        if (sp >= s && sp < 2 * s) {
-            float* p = red + (size_t)((sp - s) * WCI + wci) * 10 * 256 + lane;
-#pragma unroll
-            for (int t = 0; t < 9; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) p[(t * 4 + r) * 64] = acc[t][r];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p[(36 + r) * 64] = accb[r];
-        }
-        __syncthreads();
-        if (sp < s) {
-            const float* p = red + (size_t)(sp * WCI + wci) * 10 * 256 + lane;
-#pragma unroll
-            for (int t = 0; t < 9; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[t][r] += p[(t * 4 + r) * 64];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) accb[r] += p[(36 + r) * 64];
-        }
-        __syncthreads();
-    }
+    ksplit_reduce<WCI>(reinterpret_cast<float*>(sX), sp, wci, lane, acc, accb);
     if (sp != 0) return;
-    // lane (j, kq), register r: co = kq * 4 + r, ci = wci * 16 + j; the slab may be narrower than 16 output channels (CoutS = 4: the
-    // exact-N plan of the class convolution)
-    float* slab = a.slab + (size_t)split * 9 * a.CoutS * a.CinS;
-    float chk = 0.f;
-    const float inv = inv_d * inv_x;                       // exact: powers of two
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        note_nonfinite(chk, acc[t]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int co = kq * 4 + r, ci = wci * 16 + j;
-            if (co < a.CoutS && ci < a.CinS) slab[((size_t)t * a.CoutS + co) * a.CinS + ci] = acc[t][r] * inv;
-        }
-    }
-    report_nonfinite(a.err, chk, UAPS_ERR_WRW_NONFINITE);
-    if (want_bias && wci == 0 && j == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (kq * 4 + r < a.CoutS) a.bslab[(size_t)split * a.CoutS + kq * 4 + r] = accb[r] * inv_d;
-    }
+    store_slabs(a.slab, a.bslab, want_bias && wci == 0, split, a.CoutS, a.CinS, wci * 16, j, kq, acc, accb, inv_d, inv_x, a.err);
 }
 
 // (the *2 kernels keep two rows in flight ahead of the contraction, DEPTH 2: measured SLOWER in the step -- hrwrw<1> 60.0 -> 71.2 us,

@@ -18,7 +18,8 @@
 //     of up2_staging.hpp), then along y into the two low rows that are live -- a low row is stored when its last source row has passed.
 // The convolution is conv_hr16_body<2, false, 2>'s arithmetic: the same input scale from the dy bound, the same fp16 pieces and k order
 // (tap, channel group), the same three-product order and output scaling, the same non-finite report.  d(skip) is that kernel's, bit
-// for bit.
+// for bit.  Ring staging, weight fragments, the row of tiles and the run walk are pieces E, F, G and I of row_pieces.hpp, shared with
+// mid_bwd_row.hip; this file is the two role bodies around them, the bilinear fold and its host-side support check.
 //
 // Why the four-tap fold equals the seven-tap one.  Low-resolution index i draws on the output indices o whose source position
 // mul_rn(r, o) lies in (i - 1, i + 1): for the x2 align_corners map these are o = 2 i - 1 .. 2 i + 2 (the entry point evaluates the
@@ -36,6 +37,7 @@
 #include "conv_kernels.hpp"
 #include "conv_split.hpp"
 #include "hints.hpp"
+#include "row_pieces.hpp"
 #include "up2_staging.hpp"
 
 extern "C" int uaps_conv_get_mode(void);
@@ -68,12 +70,10 @@ __device__ __forceinline__ float up_fold_weight(float r, int o, int n_out, int n
 }
 
 __global__ __launch_bounds__(512, 2) void up_bwd_row_kernel(UpBwdArgs a) {
-    constexpr int WIDTH = 256, NSLOT = 3, ROWS = 16, NTHR = 512, NCH = 4;
-    constexpr int IW = WIDTH + 8, CGU = NSLOT * IW, PIECE = 2 * CGU, XS = 3;      // the dy ring: conv_hr16_body's image with three row slots
-    constexpr int NQ = 9 * 2, NSTEP = (NQ + 3) / 4, MW = 4, CoutP = 32;
-    constexpr int GS = WIDTH + 4;                         // channel stride of an exchange row
+    using G = RowGeom<16>;
+    constexpr int WIDTH = G::WIDTH, ROWS = G::ROWS, NTHR = 512, NCH = 4, MW = G::MW, CoutP = 32, GS = G::GS;
 
-    __shared__ __attribute__((aligned(16))) u32x4 sIn[2 * PIECE];          // [piece][channel group][slot][column]
+    __shared__ __attribute__((aligned(16))) u32x4 sIn[2 * G::PIECE];       // [piece][channel group][slot][column]
     __shared__ __attribute__((aligned(16))) float sG[2][16 * GS];          // [half][channel][column]
 
     const f32x2 sc = h16_scale(__builtin_fmaxf(bound_of(a.dy_bound, a.dy_mul), 0.f));
@@ -87,59 +87,24 @@ __global__ __launch_bounds__(512, 2) void up_bwd_row_kernel(UpBwdArgs a) {
     const int W = WIDTH, HW = a.H * W, h = a.H / 2, w = WIDTH / 2;
     const uint32_t HW4 = (uint32_t)HW * 4u, hw4 = (uint32_t)(h * w) * 4u;
 
-    const int split = xcd_swizzle(blockIdx.x, gridDim.x);
-    if (split >= a.nsplit) return;
-    const int rpi = a.H / ROWS, nruns = a.B * rpi;
-    const int run_begin = (int)((long)nruns * split / a.nsplit), run_end = (int)((long)nruns * (split + 1) / a.nsplit);
+    RowRuns rr;
+    if (!row_runs<G>(a.B, a.H, a.nsplit, rr)) return;
 
     // the margins of every row slot (image columns -4 .. -1 and 256 .. 259) are zero for the kernel's life
-    for (int e = tid; e < 2 * 2 * NSLOT * 8; e += NTHR) sIn[(e / 8) * IW + (e % 8 < 4 ? e % 8 : IW - 8 + e % 8)] = u32x4{0u, 0u, 0u, 0u};
+    zero_ring_margins<G, NTHR>(sIn, tid);
 
-    // weight fragments, once: lane (n = j, k-group kq) of step s holds k-group q = 4 s + kq = (tap q / 2, channel group q % 2) of this
-    // wave's output tile
-    u32x4 bfr[NSTEP][2];
-    int kxo[NSTEP], kyv[NSTEP];
-    {
-        const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(a.wp, (uint32_t)(2 * 9) * a.CGP * CoutP * 16u);
-#pragma unroll
-        for (int s = 0; s < NSTEP; ++s) {
-            const int q = 4 * s + kq, tap = q / 2, cgq = q % 2;
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const uint32_t off = q < NQ ? (uint32_t)(((p * 9 + tap) * a.CGP + cgq) * CoutP + half * 16 + j) * 16u : kOob;
-                bfr[s][p] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, (int)off, 0, 0);
-            }
-            const int qq = q < NQ ? q : 0;                // padded k-groups meet zero weights
-            kxo[s] = (qq % 2) * CGU + (qq / 2) % 3; kyv[s] = (qq / 2) / 3;
-        }
-    }
-    int abase[MW];
-#pragma unroll
-    for (int m = 0; m < MW; ++m) abase[m] = (wq * MW + m) * 16 + j + XS;
+    // the weight fragments of this wave's output tile (channels half * 16 .. half * 16 + 15 of the 32 packed ones), once
+    GradFrags<G> wf;
+    load_grad_frags<G, CoutP>(wf, a.wp, a.CGP, half * 16 + j, j, kq, wq * MW);
 
     // ---- staging (waves 0-3): dy channels dc0 .. dc0 + 3 = half ch of channel group cg; lane = pixels 4 lane .. 4 lane + 3 ----
     const int dc0 = wq * NCH, cg = wq >> 1, ch = wq & 1;
     f32x4 rd[NCH];
-    auto ld4 = [](__amdgpu_buffer_rsrc_t rs, uint32_t off) { return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0)); };
-    auto load_d = [&](int b, int gy, f32x4 (&dd)[NCH]) {  // every wave-instruction a 1-KiB row of one channel; rows outside the image read as zero
-        const bool ok = (unsigned)gy < (unsigned)a.H;
-        const __amdgpu_buffer_rsrc_t rs = make_rsrc(a.dy + (size_t)b * 16 * HW, 16u * HW4);
-        const uint32_t off = (uint32_t)(dc0 * HW + gy * W + lane * 4) * 4u;
-#pragma unroll
-        for (int i = 0; i < NCH; ++i) dd[i] = ld4(rs, ok ? off + (uint32_t)i * HW4 : kOob);
-    };
-    auto store_d = [&](f32x4 (&dd)[NCH], int slot) {      // this wave's four channels are two dwords of every pixel's 16-byte unit (8 channels)
+    auto load_d = [&](int b, int gy, f32x4 (&dd)[NCH]) { load_rows4<G>(a.dy, b, gy, a.H, dc0, lane, dd); };
+    auto store_d = [&](f32x4 (&dd)[NCH], int slot) {
 #pragma unroll
         for (int i = 0; i < NCH; ++i) asm volatile("" : "+v"(dd[i]));
-        const int base = (cg * NSLOT + slot) * IW + 4 + lane * 4;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            unsigned q00, q01, q10, q11;
-            conv_split2h(dd[0][k] * in_scale, dd[1][k] * in_scale, q00, q01);
-            conv_split2h(dd[2][k] * in_scale, dd[3][k] * in_scale, q10, q11);
-            *reinterpret_cast<uint2*>(reinterpret_cast<unsigned*>(&sIn[base + k]) + ch * 2) = make_uint2(q00, q10);
-            *reinterpret_cast<uint2*>(reinterpret_cast<unsigned*>(&sIn[PIECE + base + k]) + ch * 2) = make_uint2(q01, q11);
-        }
+        store_ring_rows<G>(sIn, dd, in_scale, cg, ch, lane, slot);
     };
 
     // ---- the fold (waves 4-7): this lane's low columns 2 lane and 2 lane + 1 draw on columns 4 lane - 1 .. 4 lane + 2 and
@@ -154,8 +119,8 @@ __global__ __launch_bounds__(512, 2) void up_bwd_row_kernel(UpBwdArgs a) {
 #pragma unroll
     for (int i = 0; i < NCH; ++i) { accp[i][0] = accp[i][1] = 0.f; accq[i][0] = accq[i][1] = 0.f; }
 
-    for (int run = run_begin; run < run_end; ++run) {
-        const int b = run / rpi, r0 = (run % rpi) * ROWS;
+    for (int run = rr.begin; run < rr.end; ++run) {
+        const int b = run / rr.rpi, r0 = (run % rr.rpi) * ROWS;
         // dy rows r0 - 2, r0 - 1, r0 into slots 0, 1, 2: all fetches in flight together
         if (!is_up) {
             f32x4 da[NCH], db[NCH];
@@ -175,7 +140,8 @@ __global__ __launch_bounds__(512, 2) void up_bwd_row_kernel(UpBwdArgs a) {
         for (int t = r0 - 1; t <= r0 + ROWS; ++t) {
             const bool more = t < r0 + ROWS;              // step t + 1 reads row t + 2
             if (!is_up && more) load_d(b, t + 2, rd);
-            const int s1 = s0 + 1 >= NSLOT ? s0 + 1 - NSLOT : s0 + 1, s2 = s1 + 1 >= NSLOT ? s1 + 1 - NSLOT : s1 + 1;
+            int s1, s2;
+            ring_slots<G>(s0, s1, s2);
             const bool own = t >= r0 && t < r0 + ROWS;
             // d(skip) exists on the run's own rows; d(up) also on the halo rows inside the image (wave-uniform)
             const bool work = is_up ? (unsigned)t < (unsigned)a.H : own;
@@ -184,53 +150,15 @@ __global__ __launch_bounds__(512, 2) void up_bwd_row_kernel(UpBwdArgs a) {
             f32x4 gacc[MW];
 #pragma unroll
             for (int m = 0; m < MW; ++m) gacc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (work) {
-                int aoff[NSTEP];
-#pragma unroll
-                for (int s = 0; s < NSTEP; ++s) aoff[s] = kxo[s] + (kyv[s] == 0 ? s0 : (kyv[s] == 1 ? s1 : s2)) * IW;
-                constexpr int NUN = NSTEP * MW;
-                u32x4 af[2][2];
-                auto read_a = [&](int u, u32x4 (&dst)[2]) {
-                    const int s = u / MW, m = u % MW;
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) dst[p] = sIn[p * PIECE + abase[m] + aoff[s]];
-                };
-                read_a(0, af[0]);
-#pragma unroll
-                for (int u = 0; u < NUN; ++u) {
-                    const int s = u / MW, m = u % MW;
-                    if (u + 1 < NUN) read_a(u + 1, af[(u + 1) & 1]);
-                    const auto Hf = [](const u32x4& v) { return __builtin_bit_cast(f16x8, v); };
-                    f32x4 c = gacc[m];
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(Hf(af[u & 1][1]), Hf(bfr[s][0]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(Hf(af[u & 1][0]), Hf(bfr[s][1]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(Hf(af[u & 1][0]), Hf(bfr[s][0]), c, 0, 0, 0);
-                    gacc[m] = c;
-                    if (u + 1 < NUN) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);      // next unit's DS reads first ...
-                    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);                       // ... then this unit's MFMAs
-                }
-            }
-            // lane (j, kq) holds pixels kq * 4 .. kq * 4 + 3 of channel j of every tile (a row that does not exist: zeros)
-            float chk = 0.f;
-#pragma unroll
-            for (int m = 0; m < MW; ++m) {
-                f32x4 v = gacc[m];
-                v *= out_scale_a; v *= out_scale_w;       // exact: powers of two
-                v += 0.f;                                 // (the row kernel adds its absent bias)
-                note_nonfinite(chk, v);
-                *reinterpret_cast<f32x4*>(&sG[half][j * GS + (wq * MW + m) * 16 + kq * 4]) = v;
-            }
-            report_nonfinite(a.err, chk, UAPS_ERR_CONV_NONFINITE);
+            if (work) grad_row_tiles<G>(sIn, wf, s0, s1, s2, gacc);
+            put_grad_row<G>(sG[half], gacc, out_scale_a, out_scale_w, j, kq, wq * MW, a.err);      // (a row that does not exist: zeros)
             __syncthreads();                              // every wave is done with row t - 1 of the ring; row t of both halves is complete
 
             if (!is_up) {
                 // ---- d(skip) row t out as whole 1-KiB rows ----
                 if (own) {
 #pragma unroll
-                    for (int i = 0; i < NCH; ++i) {
-                        const f32x4 gv = *reinterpret_cast<const f32x4*>(&sG[0][(dc0 + i) * GS + lane * 4]);
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, gv), rs_g, (int)((uint32_t)((dc0 + i) * HW + t * W + lane * 4) * 4u), 0, 0);
-                    }
+                    for (int i = 0; i < NCH; ++i) take_row_out<G>(sG[0], rs_g, dc0 + i, t, HW, lane);
                 }
                 if (more) store_d(rd, s0);
             } else {
@@ -335,21 +263,15 @@ extern "C" int uaps_up_bwd_fused(const float* dy, const float* wb, const float* 
     uaps::account_bytes(4.0 * B * H * W * (1.0 * Cout + 1.0 * C1 + 0.25 * C2));
     uaps::UpBwdArgs a{};
     a.dy = dy;
-    // the packed input-gradient weights (uaps_conv_pack_weights) as launch_fwd reads them for Cin = Cout, Cout = C1 + C2: the exact GEMM
-    // layout, three bf16 pieces, a header, two fp16 pieces
-    const int CGP = uaps::split_cgroups(Cout), CoP = 32;
-    const float* split_w = wb + (size_t)9 * ((Cout + 7) / 8 * 8) * CoP;
-    const size_t piece = (size_t)9 * CGP * CoP * 4;
-    a.wscale = split_w + 3 * piece + 16;
-    a.wp = split_w + 3 * piece + uaps::kH16Header;
-    a.CGP = CGP;
+    // the packed input-gradient weights (uaps_conv_pack_weights) as launch_fwd reads them for Cin = Cout, Cout = C1 + C2
+    const uaps::H16BwdWeights w16 = uaps::h16_bwd_weights(wb, C1 + C2, Cout);
+    a.wp = w16.wp; a.wscale = w16.wscale; a.CGP = w16.CGP;
     a.dskip = dskip; a.dlow = dlow;
     a.dy_bound = dy_bound; a.dy_mul = dy_mul;
     a.rh = (float)(H / 2 - 1) / (float)(H - 1); a.rw = (float)(W / 2 - 1) / (float)(W - 1);      // as uaps_up_cat_bwd
     a.err = uaps::error_word();
     a.B = B; a.H = H;
     a.nsplit = uaps_up_bwd_fused_grid(B, H);
-    const unsigned grid = (unsigned)((a.nsplit + 7) / 8 * 8);
-    UAPS_LAUNCH_MAIN(uaps::up_bwd_row_kernel, dim3(grid), dim3(512), 0, (hipStream_t)stream, a);
+    UAPS_LAUNCH_MAIN(uaps::up_bwd_row_kernel, dim3(uaps::row_grid(a.nsplit)), dim3(512), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

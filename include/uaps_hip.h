@@ -1332,6 +1332,57 @@ int uaps_rle_encode(const uaps_rle_call* call);
 int uaps_rle_decode(const uaps_rle_call* call);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mask clean-up morphology: csrc/morph.hip.
+ *
+ * uaps_morphology: a chain of n_steps steps (op, footprint, radius), applied in order, on a label map.  mask and out int64
+ *   [B, H, W], out != mask.
+ *   Footprint of radius r: the offsets (dy, dx) with |dy| <= r and |dx| <= w(dy); square w = r, cross (the L1 ball) w = r - |dy|,
+ *   disk w = floor(sqrt(r * r - dy * dy)) formed in integers.
+ *   Border: erosion takes what lies outside the image as foreground, dilation as background (scipy's border_value 1 and 0), so an
+ *   opening does not eat a defect that touches the edge; opening stays anti-extensive, closing extensive.
+ *   One step: for every selected class c (classes[0 .. n_classes), any order), on the plane P_c = (mask == c) alone,
+ *     R_c = P_c - S (erode), P_c + S (dilate), (P_c - S) + S (open), (P_c + S) - S (close), P_c \ (P_c - S) (boundary).
+ *   Then per pixel p of value m: m selected and p in R_m: stays m.  Otherwise m neither `background` nor selected (an ignore label,
+ *   a class the call does not name): stays m -- such pixels are obstacles, never claimed.  Otherwise (background, or just removed):
+ *   the smallest selected c with p in R_c, `background` if there is none.  The next step sees that map.
+ *   One launch for the whole chain; a workgroup holds a band of rows (of at most 512 columns) and a halo of `reach` rows -- the sum
+ *   of r over erode / dilate / boundary steps and of 2 r over open / close steps -- as bit planes in at most 64 KiB of LDS.
+ *   band_rows 0: the band height uaps_morph_band_rows reports; > 0: that height (every height gives the same bits).  No workspace,
+ *   no atomics, no synchronisation with the host.
+ * uaps_morph_band_rows (host only): the band height 0 resolves to for n_planes = n_classes + 1 bit planes (the selected classes and
+ *   the obstacle plane).  UAPS_EINVAL rows == NULL, a non-positive dimension, n_planes outside [2, 9], reach < 1; UAPS_ERANGE as below.
+ * Errors (nothing launched): UAPS_EINVAL null struct, mask or out, out == mask, non-positive dimension, n_steps outside [1, 8], an
+ *   unknown op or footprint, n_classes outside [1, 8], a duplicate class or one equal to `background`, negative band_rows, struct_size
+ *   below this version's; UAPS_ERANGE a radius outside [1, 15], reach > 64, H or W above 4096, B * H * W * 8 >= 2 GiB, a forced
+ *   band_rows whose planes do not fit.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_MORPH_ERODE 0
+#define UAPS_MORPH_DILATE 1
+#define UAPS_MORPH_OPEN 2
+#define UAPS_MORPH_CLOSE 3
+#define UAPS_MORPH_BOUNDARY 4
+#define UAPS_MORPH_SQUARE 0
+#define UAPS_MORPH_CROSS 1
+#define UAPS_MORPH_DISK 2
+#define UAPS_MORPH_MAX_STEPS 8
+#define UAPS_MORPH_MAX_CLASSES 8
+typedef struct uaps_morph_call {
+    size_t struct_size;
+    int32_t B, H, W;
+    int32_t n_steps;
+    int32_t op[UAPS_MORPH_MAX_STEPS], footprint[UAPS_MORPH_MAX_STEPS], radius[UAPS_MORPH_MAX_STEPS];
+    int32_t n_classes;
+    int32_t classes[UAPS_MORPH_MAX_CLASSES];
+    int32_t background;
+    int32_t band_rows;                           /* 0: chosen by the library; > 0: forced (tests) */
+    const int64_t* mask;                         /* [B][H][W] */
+    int64_t* out;                                /* [B][H][W] */
+    uaps_stream_t stream;
+} uaps_morph_call;
+int uaps_morphology(const uaps_morph_call* call);
+int uaps_morph_band_rows(int H, int W, int n_planes, int reach, int* rows);
+
+/* ---------------------------------------------------------------------------------------------
  * Tiled (sliding-window) full-resolution inference: csrc/tiled.hip.  An image of any size is cut into overlapping tiles of the size
  * the network runs at, the network runs on the tiles, and the tiles' probability maps are blended under a separable window.
  *

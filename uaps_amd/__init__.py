@@ -39,6 +39,9 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   score_curves, plane_curves, CurveResult, CurveSums  threshold-sweep metrics from histograms of quantised scores: pixel AUROC, AP,
                                                     AUPRO, ECE, and AUROC / AURC of the uncertainty map;
                                                     inference.evaluate(..., curves=True)
+  morphology                                        mask clean-up on a label map: a fused chain of erode / dilate / open / close /
+                                                    boundary steps (square, cross, disk; radius 1..15);
+                                                    inference.predict_instances(..., cleanup=steps), inference.evaluate(..., cleanup=steps)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -72,6 +75,7 @@ from .matching import match_instances, MatchResult, MATCH_COLUMNS
 from . import matching
 from .curves import score_curves, plane_curves, CurveResult, CurveSums
 from . import curves
+from .morphology import morphology          # (the function takes the submodule's name: uaps_amd.morphology(mask, steps, C))
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -172,6 +172,8 @@ SIGNATURES = {
     "uaps_rle_count": (C.c_int, [_PTR]),
     "uaps_rle_encode": (C.c_int, [_PTR]),
     "uaps_rle_decode": (C.c_int, [_PTR]),
+    "uaps_morphology": (C.c_int, [_PTR]),
+    "uaps_morph_band_rows": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)]),
     "uaps_tile_origins": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     "uaps_tile_cut": (C.c_int, [_PTR]),
     "uaps_tile_fold": (C.c_int, [_PTR]),
@@ -358,6 +360,19 @@ class RleCall(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_classes", C.c_int32),
                 ("classes", C.c_int64 * RLE_MAX_CLASSES), ("mask", C.c_void_p), ("col_offsets", C.c_void_p), ("pairs", C.c_void_p),
                 ("offsets", C.c_void_p), ("n_runs", C.c_int64), ("out", C.c_void_p), ("out_uint8", C.c_int32), ("stream", C.c_void_p)]
+
+
+MORPH_MAX_STEPS, MORPH_MAX_CLASSES = 8, 8   # UAPS_MORPH_MAX_STEPS, UAPS_MORPH_MAX_CLASSES
+MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3, "boundary": 4}     # UAPS_MORPH_ERODE ..
+MORPH_FOOTPRINTS = {"square": 0, "cross": 1, "disk": 2}                         # UAPS_MORPH_SQUARE ..
+
+
+class MorphCall(C.Structure):
+    """uaps_morph_call (include/uaps_hip.h): every operand of uaps_morphology, size-versioned."""
+    _fields_ = [("struct_size", C.c_size_t), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_steps", C.c_int32),
+                ("op", C.c_int32 * MORPH_MAX_STEPS), ("footprint", C.c_int32 * MORPH_MAX_STEPS), ("radius", C.c_int32 * MORPH_MAX_STEPS),
+                ("n_classes", C.c_int32), ("classes", C.c_int32 * MORPH_MAX_CLASSES), ("background", C.c_int32),
+                ("band_rows", C.c_int32), ("mask", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p)]
 
 
 TILE_MAX_CHUNKS, TILE_MAX_MAPS = 32, 2  # UAPS_TILE_MAX_CHUNKS, UAPS_TILE_MAX_MAPS

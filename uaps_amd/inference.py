@@ -196,6 +196,17 @@ def _instance_sums(scored: torch.Tensor, y: torch.Tensor, kw) -> torch.Tensor:
     return match_instances(pred, target, scored.shape[1], iou_threshold=kw.get("iou_threshold", 0.5)).sums(kw.get("classes"))
 
 
+def _cleaned(mask: torch.Tensor, cleanup, num_classes: int) -> torch.Tensor:
+    """The arg-max mask after the clean-up chain `cleanup` (morphology.morphology's `steps`)."""
+    from .morphology import morphology
+    return morphology(mask, cleanup, num_classes)
+
+
+def _one_hot_maps(mask: torch.Tensor, num_classes: int) -> torch.Tensor:
+    """float32 [B,C,H,W] maps whose arg-max is `mask`: what the scoring kernels take in place of logits."""
+    return torch.nn.functional.one_hot(mask, num_classes).permute(0, 3, 1, 2).contiguous().float()
+
+
 _CURVE_KEYS = {"bins", "fpr_limit", "ece_bins", "classes", "max_instances", "connectivity", "min_area", "uncertainty", "lo", "hi"}
 
 
@@ -233,7 +244,7 @@ def _uncertainty_sums(heads, y: torch.Tensor, kw):
 
 @torch.no_grad()
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None, tiled=None,
-             surface=None, instances=None, curves=None) -> Dict[str, float]:
+             surface=None, instances=None, curves=None, cleanup=None) -> Dict[str, float]:
     """The score table of notebook cell 25: mIoU, mDice and pixel accuracy of the main head computed image by image
     (utilities/metrics.py conventions) and averaged over the images, in percent.  tta=True, or a tuple of scales: the arg-max of the
     multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main head's.  tiled=True, or a dict of
@@ -252,8 +263,15 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     default 0.3, over the defects of the labels), "ECE(%)" (ece_bins groups, default 16) and "curve_images_skipped" (images with more
     real defects than max_instances are left out).  uncertainty=True (plain path only, a model with an auxiliary head) adds
     "UncAUROC(%)" and "AURC": how well consistency.uncertainty_map(main, aux1), binned over [lo, hi] (default 0, 1), marks the wrong
-    pixels of the main head.  Summed on the device; one copy at the end."""
+    pixels of the main head.  Summed on the device; one copy at the end.
+    cleanup: a morphology.morphology `steps` sequence.  The surface= and instances= branches then score the cleaned arg-max of the
+    scored maps, and "mIoU_clean(%)" and "mDice_clean(%)" are added: the same per-image rule on the cleaned mask.  Every other key
+    (the curves among them: they score maps, not masks) is what it is without cleanup."""
     miou, mdice, acc = [], [], []
+    miou_clean, mdice_clean = [], []
+    if cleanup is not None:
+        from .morphology import check_steps
+        cleanup = check_steps(cleanup)
     curve_kw = _curves_kwargs(curves, tta, tiled) if curves is not None and curves is not False else None      # ({}: the defaults)
     curve_sums = unc_sums = None
     tiled_kw = _tiled_kwargs(tiled, tta, "evaluate") if tiled else None
@@ -277,16 +295,24 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         if curve_kw is not None:
             part = _curve_sums(scored, y, curve_kw, from_logits=tiled_kw is None and not tta)
             curve_sums = part if curve_sums is None else curve_sums + part
+        masked = scored                                      # what the mask-level scores (surface, instances) look at
+        if cleanup is not None:
+            masked = _one_hot_maps(_cleaned(torch.argmax(scored, dim=1), cleanup, scored.shape[1]), scored.shape[1])
+            for cm in metrics.seg_confusion_per_image(masked, y).cpu().numpy():
+                m = metrics.metrics_from_confusion(cm)
+                miou_clean.append(m["miou"]); mdice_clean.append(m["mdice"])
         if surf_kw is not None:
-            surf_sums.append(_surface_sums(scored, y, surf_kw))
+            surf_sums.append(_surface_sums(masked, y, surf_kw))
         if inst_kw is not None:
-            inst_sums.append(_instance_sums(scored, y, inst_kw))
+            inst_sums.append(_instance_sums(masked, y, inst_kw))
         cms = metrics.seg_confusion_per_image(scored, y).cpu().numpy()
         for cm in cms:
             m = metrics.metrics_from_confusion(cm)
             miou.append(m["miou"]); mdice.append(m["mdice"]); acc.append(m["acc"])
     out = {"mIoU(%)": float(np.mean(miou) * 100), "mDice(%)": float(np.mean(mdice) * 100), "Accuracy(%)": float(np.mean(acc) * 100),
            "images": len(acc)}
+    if cleanup is not None:
+        out["mIoU_clean(%)"], out["mDice_clean(%)"] = float(np.mean(miou_clean) * 100), float(np.mean(mdice_clean) * 100)
     if surf_kw is not None:
         tot = torch.stack(surf_sums).sum(dim=0).cpu().tolist() if surf_sums else [0.0] * 4
         pairs = int(tot[3])
@@ -328,20 +354,25 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
 
 @torch.no_grad()
 def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, tiled=None, min_area: int = 1, connectivity: int = 8,
-                      max_instances: int = 256):
+                      max_instances: int = 256, cleanup=None):
     """Defects instead of pixels: instances.label_instances on the main head's arg-max mask, with maps = (confidence, uncertainty).
     The confidence is the main head's largest softmax; with tta (True, or a tuple of scales) mask and confidence are those of
     tta.predict_tta.  The uncertainty is consistency.uncertainty_map(main, aux1) of the plain forward where the model has an auxiliary
     head; a one-head model gets the confidence alone.  tiled (True, or a dict of tiled.predict_tiled keywords): mask, confidence and
-    the blended per-tile uncertainty of sliding-window inference, for images of any size.  Returns an instances.InstanceResult
-    (records() lists the defects)."""
+    the blended per-tile uncertainty of sliding-window inference, for images of any size.  cleanup (a morphology.morphology `steps`
+    sequence): the arg-max mask goes through that chain before it is labelled, under all three paths; the maps are untouched.  Returns an
+    instances.InstanceResult (records() lists the defects)."""
     from . import instances
     if tiled:
         from .tiled import predict_tiled
-        kw = {**_tiled_kwargs(tiled, tta, "predict_instances"), "want": ("mask", "conf")}
+        # (the class count of the clean-up is the blended maps' channel count: they are asked for beside the mask then)
+        kw = {**_tiled_kwargs(tiled, tta, "predict_instances"), "want": ("mask", "conf") + (("probs",) if cleanup is not None else ())}
         kw.setdefault("uncertainty", "auto")
         r = predict_tiled(model, images, **kw)
-        return instances.label_instances(r.mask, (r.conf,) + tuple(r.maps), connectivity=connectivity, min_area=min_area,
+        mask = r.mask
+        if cleanup is not None:
+            mask = _cleaned(mask, cleanup, r.probs.shape[1])
+        return instances.label_instances(mask, (r.conf,) + tuple(r.maps), connectivity=connectivity, min_area=min_area,
                                          max_instances=max_instances)
     mask, heads = predict(model, images)
     if tta:
@@ -351,6 +382,8 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     else:
         conf = torch.softmax(heads[0], dim=1).amax(dim=1)
     maps = (conf,) if len(heads) < 2 else (conf, consistency.uncertainty_map(heads[0], heads[1]))
+    if cleanup is not None:
+        mask = _cleaned(mask, cleanup, heads[0].shape[1])
     return instances.label_instances(mask, maps, connectivity=connectivity, min_area=min_area, max_instances=max_instances)
 
 

@@ -1383,6 +1383,60 @@ int uaps_morphology(const uaps_morph_call* call);
 int uaps_morph_band_rows(int H, int W, int n_planes, int reach, int* rows);
 
 /* ---------------------------------------------------------------------------------------------
+ * Component clean-up of a label map: csrc/components.hip (the labelling passes: csrc/cc_common.hpp, shared with csrc/instances.hip).
+ *
+ * uaps_components: a chain of n_steps steps (kind, n), applied in order, on a label map.  mask and out int64 [B, H, W], out != mask,
+ *   any H, W >= 1.  A component is a maximal set of equal-valued pixels connected under `connectivity` (4 or 8), as
+ *   uaps_label_instances defines it.  classes[0 .. n_classes) are the selected classes, in any order.
+ *     UAPS_COMP_AREA_OPEN, n >= 1   every component of a selected class with fewer than n pixels becomes `background` (area >= n stays:
+ *                                   the keep rule of uaps_label_instances' min_area).
+ *     UAPS_COMP_CLEAR_BORDER        every component of a selected class with a pixel in row 0, row H - 1, column 0 or column W - 1
+ *                                   becomes `background`; n is not read.
+ *     UAPS_COMP_FILL_HOLES, n >= 1  for every selected class c, a hole of c is a connected component of the complement of
+ *                                   P_c = (mask == c) -- background, other classes and ignore labels alike -- that has no pixel on the
+ *                                   image border, connected under the COMPLEMENTARY connectivity (4 where connectivity == 8, 8 where
+ *                                   it is 4).  A hole of at most n pixels (all of its pixels count, not only the background ones) is
+ *                                   filled; n = UAPS_COMP_ALL: every hole.  All planes are evaluated on the step's input; only pixels
+ *                                   whose value is `background` are rewritten, and one that lies in a filled hole of several classes
+ *                                   goes to the smallest of them.  Every other pixel inside a hole stays and is never claimed.
+ *   Area opening and clear border only ever write `background`, and only over pixels of selected classes.
+ *   Launches per step: tile-local union-find in LDS, seam merging with agent-scope atomics, flatten + area + border flag, one apply
+ *   pass that writes the step's map once (hole filling labels B * n_classes virtual planes read from the map; no one-hot tensor).
+ *   Integer atomics only: the same bits from run to run.  No workgroup waits for another inside a launch.  The call does not
+ *   synchronise; the area and flag words are zeroed inside the call for every step.
+ *   workspace: uaps_components_workspace_bytes(B, H, W, n_planes) bytes, 256-byte aligned, the call's alone until it has run;
+ *   n_planes = n_classes for a chain with a UAPS_COMP_FILL_HOLES step, 1 for a chain without.
+ * Errors (nothing launched): UAPS_EINVAL null struct, mask, out or workspace, out == mask, non-positive dimension, n_steps outside
+ *   [1, 8], an unknown kind, n < 1 in an area-open or hole-filling step, n_classes outside [1, 8], a duplicate class or one equal to
+ *   `background`, connectivity outside {4, 8}, struct_size below this version's (uaps_components_workspace_bytes: bytes == NULL,
+ *   non-positive dimension, n_classes outside [1, 8]); UAPS_ERANGE H * W >= 2^31, B * H * W * 8 >= 2 GiB, a workspace of 2 GiB or
+ *   more (by dimensions); UAPS_EWORKSPACE a workspace smaller than that or not 256-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_COMP_AREA_OPEN 0
+#define UAPS_COMP_CLEAR_BORDER 1
+#define UAPS_COMP_FILL_HOLES 2
+#define UAPS_COMP_MAX_STEPS 8
+#define UAPS_COMP_MAX_CLASSES 8
+#define UAPS_COMP_ALL 2147483647                 /* n of a hole-filling step: every hole, whatever its area */
+typedef struct uaps_components_call {
+    size_t struct_size;
+    int32_t B, H, W;
+    int32_t n_steps;
+    int32_t kind[UAPS_COMP_MAX_STEPS], n[UAPS_COMP_MAX_STEPS];
+    int32_t n_classes;
+    int32_t classes[UAPS_COMP_MAX_CLASSES];
+    int32_t background;
+    int32_t connectivity;                        /* 4 or 8: of the defects; holes take the other one */
+    const int64_t* mask;                         /* [B][H][W] */
+    int64_t* out;                                /* [B][H][W] */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_components_call;
+int uaps_components_workspace_bytes(int B, int H, int W, int n_classes, size_t* bytes);
+int uaps_components(const uaps_components_call* call);
+
+/* ---------------------------------------------------------------------------------------------
  * Tiled (sliding-window) full-resolution inference: csrc/tiled.hip.  An image of any size is cut into overlapping tiles of the size
  * the network runs at, the network runs on the tiles, and the tiles' probability maps are blended under a separable window.
  *

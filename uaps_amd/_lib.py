@@ -174,6 +174,8 @@ SIGNATURES = {
     "uaps_rle_decode": (C.c_int, [_PTR]),
     "uaps_morphology": (C.c_int, [_PTR]),
     "uaps_morph_band_rows": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)]),
+    "uaps_components_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
+    "uaps_components": (C.c_int, [_PTR]),
     "uaps_tile_origins": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     "uaps_tile_cut": (C.c_int, [_PTR]),
     "uaps_tile_fold": (C.c_int, [_PTR]),
@@ -373,6 +375,19 @@ class MorphCall(C.Structure):
                 ("op", C.c_int32 * MORPH_MAX_STEPS), ("footprint", C.c_int32 * MORPH_MAX_STEPS), ("radius", C.c_int32 * MORPH_MAX_STEPS),
                 ("n_classes", C.c_int32), ("classes", C.c_int32 * MORPH_MAX_CLASSES), ("background", C.c_int32),
                 ("band_rows", C.c_int32), ("mask", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+COMP_MAX_STEPS, COMP_MAX_CLASSES, COMP_ALL = 8, 8, 2 ** 31 - 1       # UAPS_COMP_MAX_STEPS, UAPS_COMP_MAX_CLASSES, UAPS_COMP_ALL
+COMP_KINDS = {"area_open": 0, "clear_border": 1, "fill_holes": 2}      # UAPS_COMP_AREA_OPEN ..
+
+
+class ComponentsCall(C.Structure):
+    """uaps_components_call (include/uaps_hip.h): every operand of uaps_components, size-versioned."""
+    _fields_ = [("struct_size", C.c_size_t), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_steps", C.c_int32),
+                ("kind", C.c_int32 * COMP_MAX_STEPS), ("n", C.c_int32 * COMP_MAX_STEPS), ("n_classes", C.c_int32),
+                ("classes", C.c_int32 * COMP_MAX_CLASSES), ("background", C.c_int32), ("connectivity", C.c_int32),
+                ("mask", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
 
 
 TILE_MAX_CHUNKS, TILE_MAX_MAPS = 32, 2  # UAPS_TILE_MAX_CHUNKS, UAPS_TILE_MAX_MAPS

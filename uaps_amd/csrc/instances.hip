@@ -7,12 +7,13 @@
 //                          pixel's parent := the image-local index of its tile-local root (the smallest raster index of the tile-local
 //                          component; tile-local raster order and image raster order agree inside a tile).  Plain stores; the area
 //                          scratch word of every pixel is zeroed on the way.
-//   2 seam_merge_kernel    one lane per seam pixel (first row / first column of a tile) and its up to three neighbours across the seam.
+//   2 seam_merge_kernel    one lane per seam pixel (first row / first column of a tile) and its up to three neighbours across the seam
+//                          (only the joins the tile pass does not already imply: cc_common.hpp).
 //                          Every parent word is read with relaxed agent-scope atomic loads and lowered with atomicMin.  A stale read is
 //                          an older parent, still an ancestor in the same component, so it costs iterations, never correctness.
-//   3 flatten_area_kernel  parent -> root (the component's smallest pixel index = its first pixel), stored into `labels`; one integer
-//                          atomicAdd per run of equal roots inside a wave onto the root's area word (whole groups of 64 pixels of one
-//                          root are carried on by the wave over its 16 groups first).
+//   3 flatten_area_kernel  parent -> root (the component's smallest pixel index = its first pixel), stored into `labels`; integer
+//                          atomicAdds onto the roots' area words: the lanes of a 64-pixel group's leading root are counted by ballot
+//                          and carried on by the wave over its 16 groups, the other roots send one add per run of equal roots.
 //   4 chunk_count_kernel / scan_segments_kernel / number_roots_kernel
 //                          "is a root and area >= min_area" counted per 256-pixel raster chunk, the chunk counts scanned per image
 //                          (count[b] = the total), the surviving roots numbered 1..N_b in raster order; the root's lane writes the
@@ -28,198 +29,31 @@
 // rows, so that a wave reads 64 consecutive words of a row.  A run starts where the previous pixel of the walk is not of the class and
 // ends where the next one is not; the k-th start and the k-th end of a plane belong together, so starts and ends are written
 // independently and a last launch turns ends into lengths.
+//
+// Launches 1 to 3 and the union-find under them live in cc_common.hpp, shared with components.hip; here they run with the policy
+// "equal values belong together, the background forms nothing" and without the border flag.
 #include <string.h>
-#include "loss_common.hpp"
+#include "cc_common.hpp"
 
 namespace {
 using namespace uaps::loss;
+using namespace uaps::cc;                  // the union-find and the three labelling passes, shared with components.hip
 
-constexpr int kTW = 16, kTH = 16, kTile = kTW * kTH, kPer = kTile / kThreads;   // pixels of a tile per lane
 constexpr int kChunk = kThreads;                                                // raster chunk of the numbering scan
 constexpr int kMaxGrid = 1 << 24;
 
-__device__ __forceinline__ int ld_agent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int ld_wg(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-// parent[x] <= x always and only ever decreases: a walk strictly descends and ends at a word that names itself
-template <bool GLOBAL>
-__device__ __forceinline__ int uf_find(const int* par, int a) {
-    for (;;) {
-        const int p = GLOBAL ? ld_agent(par + a) : ld_wg(par + a);
-        if (p == a) return a;
-        a = p;
-    }
-}
-
-// parent words are final when flatten_area_kernel runs (the launch boundary made them visible): plain loads
-__device__ __forceinline__ int uf_find_plain(const int* par, int a) {
-    for (;;) {
-        const int p = par[a];
-        if (p == a) return a;
-        a = p;
-    }
-}
-
-// joins the trees of a and b: the larger root is lowered onto the smaller one.  A failed atomicMin means somebody else lowered that
-// word in the meantime: go on from what it holds now, which is smaller -- nothing here waits for another lane's progress.
-template <bool GLOBAL>
-__device__ __forceinline__ void uf_union(int* par, int a, int b) {
-    for (;;) {
-        a = uf_find<GLOBAL>(par, a);
-        b = uf_find<GLOBAL>(par, b);
-        if (a == b) return;
-        if (a > b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(par + b, a);
-        if (old == b) return;
-        b = old;
-    }
-}
-
-struct LabelArgs {
-    int B, H, W, ntx, nty, conn8, has_bg;
-    long long bg;
-    const long long* mask;
-    int* parent;
-    int* area;
-};
+using LabelArgs = CcArgs<SameValuePolicy>;
 
 __global__ __launch_bounds__(kThreads) void tile_label_kernel(LabelArgs a) {
     __shared__ long long cls[kTile];
     __shared__ int lab[kTile];
-    const long tiles = (long)a.ntx * a.nty;
-    const long blk = blockIdx.x;
-    const int b = (int)(blk / tiles);
-    const int t = (int)(blk - (long)b * tiles);
-    const int ty = t / a.ntx, tx = t - ty * a.ntx;
-    const long HW = (long)a.H * a.W;
-    const long long* m = a.mask + (long)b * HW;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        const int li = threadIdx.x + k * kThreads, ly = li / kTW, lx = li % kTW;
-        const int y = ty * kTH + ly, x = tx * kTW + lx;
-        long long c = 0;
-        bool fg = false;
-        if (y < a.H && x < a.W) {
-            c = m[(long)y * a.W + x];
-            fg = !(a.has_bg && c == a.bg);
-        }
-        cls[li] = c;
-        lab[li] = fg ? li : -1;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        const int li = threadIdx.x + k * kThreads, ly = li / kTW, lx = li % kTW;
-        if (lab[li] < 0) continue;             // (-1 never changes; a foreground word stays >= 0)
-        const long long c = cls[li];
-        if (lx > 0 && lab[li - 1] >= 0 && cls[li - 1] == c) uf_union<false>(lab, li, li - 1);
-        if (ly > 0) {
-            if (lab[li - kTW] >= 0 && cls[li - kTW] == c) uf_union<false>(lab, li, li - kTW);
-            if (a.conn8) {
-                if (lx > 0 && lab[li - kTW - 1] >= 0 && cls[li - kTW - 1] == c) uf_union<false>(lab, li, li - kTW - 1);
-                if (lx < kTW - 1 && lab[li - kTW + 1] >= 0 && cls[li - kTW + 1] == c) uf_union<false>(lab, li, li - kTW + 1);
-            }
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        const int li = threadIdx.x + k * kThreads, ly = li / kTW, lx = li % kTW;
-        const int y = ty * kTH + ly, x = tx * kTW + lx;
-        if (y >= a.H || x >= a.W) continue;
-        int out = -1;
-        if (lab[li] >= 0) {
-            const int r = uf_find<false>(lab, li);
-            out = (ty * kTH + r / kTW) * a.W + tx * kTW + r % kTW;
-        }
-        const long n = (long)b * HW + (long)y * a.W + x;
-        a.parent[n] = out;
-        a.area[n] = 0;
-    }
+    cc_tile_label(a, cls, lab);
 }
 
-// per image: (nty - 1) * W pixels on the first row of a tile row, then (ntx - 1) * H pixels on the first column of a tile column
-__global__ __launch_bounds__(kThreads) void seam_merge_kernel(LabelArgs a) {
-    const long HW = (long)a.H * a.W;
-    const long nH = (long)(a.nty - 1) * a.W, per = nH + (long)(a.ntx - 1) * a.H, total = (long)a.B * per;
-    for (long g = (long)blockIdx.x * kThreads + threadIdx.x; g < total; g += (long)gridDim.x * kThreads) {
-        const int b = (int)(g / per);
-        long j = g - (long)b * per;
-        const long long* m = a.mask + (long)b * HW;
-        int* par = a.parent + (long)b * HW;
-        int y, x, dy[3], dx[3];
-        if (j < nH) {                           // the three neighbours in the row above
-            y = ((int)(j / a.W) + 1) * kTH; x = (int)(j % a.W);
-            dy[0] = -1; dx[0] = 0; dy[1] = -1; dx[1] = -1; dy[2] = -1; dx[2] = 1;
-        } else {                                // the three neighbours in the column to the left
-            j -= nH;
-            x = ((int)(j / a.H) + 1) * kTW; y = (int)(j % a.H);
-            dy[0] = 0; dx[0] = -1; dy[1] = -1; dx[1] = -1; dy[2] = 1; dx[2] = -1;
-        }
-        const int p = y * a.W + x;
-        const long long c = m[p];
-        if (a.has_bg && c == a.bg) continue;
-        const int nn = a.conn8 ? 3 : 1;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (k >= nn) break;
-            const int yy = y + dy[k], xx = x + dx[k];
-            if (yy < 0 || yy >= a.H || xx < 0 || xx >= a.W) continue;
-            const int q = yy * a.W + xx;
-            if (m[q] == c) uf_union<true>(par, p, q);
-        }
-    }
-}
-
-// the last lane of the run of lanes that lane `lane` belongs to; heads = ballot of the runs' first lanes (bit 0 set)
-__device__ __forceinline__ int run_end(unsigned long long heads, int lane) {
-    const unsigned long long above = lane < 63 ? heads >> (lane + 1) : 0ull;
-    return above ? lane + __builtin_ctzll(above) : 63;
-}
-
-// A wave walks kSpan consecutive groups of 64 pixels and carries what a whole group of ONE key contributed (`pending`, wave-uniform)
-// into the next group: a component that fills rows sends one atomic per kSpan * 64 pixels instead of one per 64.
-constexpr int kSpan = 16;
-inline int span_grid(long N) { return (int)((N + (long)kThreads * kSpan - 1) / ((long)kThreads * kSpan)); }
+__global__ __launch_bounds__(kThreads) void seam_merge_kernel(LabelArgs a) { cc_seam_merge(a); }
 
 __global__ __launch_bounds__(kThreads) void flatten_area_kernel(const int* __restrict__ parent, int* __restrict__ roots, int* area, long HW, long N) {
-    const int lane = threadIdx.x & 63;
-    const long w0 = ((long)blockIdx.x * kWaves + (threadIdx.x >> 6)) * (kSpan * 64);
-    long pend_b = -1;
-    int pend_r = -1, pend_n = 0;
-    for (int it = 0; it < kSpan; ++it) {
-        const long base = w0 + (long)it * 64;
-        if (base >= N) break;                  // (wave-uniform)
-        const long n = base + lane;
-        const bool valid = n < N;
-        int r = -2;
-        long b = 0, i = 0;
-        if (valid) {
-            b = n / HW; i = n - b * HW;
-            const int* par = parent + b * HW;
-            r = par[i];
-            if (r >= 0) r = uf_find_plain(par, r);
-            roots[n] = r;
-        }
-        const int prev = __shfl_up(r, 1, 64);
-        const bool head = lane == 0 || prev != r || i == 0;
-        const unsigned long long heads = __ballot(head);
-        const int r0 = __shfl(r, 0, 64);
-        const long b0 = __shfl(b, 0, 64);
-        if (heads == 1ull && r0 >= 0) {        // the whole group is one run of one root (lane 63 is valid: its r equals r0 >= 0)
-            if (pend_n > 0 && pend_r == r0 && pend_b == b0) {
-                pend_n += 64;
-            } else {
-                if (pend_n > 0 && lane == 0) atomicAdd(area + pend_b * HW + pend_r, pend_n);
-                pend_b = b0; pend_r = r0; pend_n = 64;
-            }
-            continue;
-        }
-        if (pend_n > 0 && lane == 0) atomicAdd(area + pend_b * HW + pend_r, pend_n);
-        pend_n = 0;
-        if (head && r >= 0) atomicAdd(area + b * HW + r, run_end(heads, lane) - lane + 1);
-    }
-    if (pend_n > 0 && lane == 0) atomicAdd(area + pend_b * HW + pend_r, pend_n);
+    cc_flatten_area<false>(parent, roots, area, HW, N, 0, 0);
 }
 
 struct NumberArgs {
@@ -561,8 +395,8 @@ extern "C" int uaps_label_instances(const uaps_instances_call* call) {
     const hipError_t e = hipMemsetAsync(c.table, 0, (size_t)c.B * c.max_instances * 72, st);
     if (e != hipSuccess) return (int)e;
     LabelArgs la;
-    la.B = c.B; la.H = c.H; la.W = c.W; la.ntx = (c.W + kTW - 1) / kTW; la.nty = (c.H + kTH - 1) / kTH;
-    la.conn8 = c.connectivity == 8; la.has_bg = c.has_background; la.bg = c.background;
+    la.Q = c.B; la.H = c.H; la.W = c.W; la.ntx = (c.W + kTW - 1) / kTW; la.nty = (c.H + kTH - 1) / kTH;
+    la.conn8 = c.connectivity == 8; la.pol.has_bg = c.has_background; la.pol.bg = c.background;
     la.mask = (const long long*)c.mask; la.parent = parent; la.area = area;
     const long tiles = (long)c.B * la.ntx * la.nty;             // < 2^28: every tile holds a pixel
     UAPS_LAUNCH_MAIN(tile_label_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, st, la);

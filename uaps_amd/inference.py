@@ -196,10 +196,16 @@ def _instance_sums(scored: torch.Tensor, y: torch.Tensor, kw) -> torch.Tensor:
     return match_instances(pred, target, scored.shape[1], iou_threshold=kw.get("iou_threshold", 0.5)).sums(kw.get("classes"))
 
 
-def _cleaned(mask: torch.Tensor, cleanup, num_classes: int) -> torch.Tensor:
-    """The arg-max mask after the clean-up chain `cleanup` (morphology.morphology's `steps`)."""
-    from .morphology import morphology
-    return morphology(mask, cleanup, num_classes)
+def _cleaned(mask: torch.Tensor, cleanup, num_classes: int, components=None) -> torch.Tensor:
+    """The arg-max mask after the clean-up chain `cleanup` (morphology.morphology's `steps`), then after the component chain
+    `components` (components.components' `steps`); either may be None."""
+    if cleanup is not None:
+        from .morphology import morphology
+        mask = morphology(mask, cleanup, num_classes)
+    if components is not None:
+        from .components import components as component_steps
+        mask = component_steps(mask, components, num_classes)
+    return mask
 
 
 def _one_hot_maps(mask: torch.Tensor, num_classes: int) -> torch.Tensor:
@@ -244,7 +250,7 @@ def _uncertainty_sums(heads, y: torch.Tensor, kw):
 
 @torch.no_grad()
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None, tiled=None,
-             surface=None, instances=None, curves=None, cleanup=None) -> Dict[str, float]:
+             surface=None, instances=None, curves=None, cleanup=None, components=None) -> Dict[str, float]:
     """The score table of notebook cell 25: mIoU, mDice and pixel accuracy of the main head computed image by image
     (utilities/metrics.py conventions) and averaged over the images, in percent.  tta=True, or a tuple of scales: the arg-max of the
     multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main head's.  tiled=True, or a dict of
@@ -266,12 +272,18 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     pixels of the main head.  Summed on the device; one copy at the end.
     cleanup: a morphology.morphology `steps` sequence.  The surface= and instances= branches then score the cleaned arg-max of the
     scored maps, and "mIoU_clean(%)" and "mDice_clean(%)" are added: the same per-image rule on the cleaned mask.  Every other key
-    (the curves among them: they score maps, not masks) is what it is without cleanup."""
+    (the curves among them: they score maps, not masks) is what it is without cleanup.
+    components: a components.components `steps` sequence (area_open / clear_border / fill_holes), applied to the arg-max mask after
+    the cleanup chain where one is given; the same branches and the same two keys then see the mask after both."""
     miou, mdice, acc = [], [], []
     miou_clean, mdice_clean = [], []
     if cleanup is not None:
         from .morphology import check_steps
         cleanup = check_steps(cleanup)
+    if components is not None:
+        from .components import check_steps as check_component_steps
+        components = check_component_steps(components)
+    clean = cleanup is not None or components is not None
     curve_kw = _curves_kwargs(curves, tta, tiled) if curves is not None and curves is not False else None      # ({}: the defaults)
     curve_sums = unc_sums = None
     tiled_kw = _tiled_kwargs(tiled, tta, "evaluate") if tiled else None
@@ -296,8 +308,8 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
             part = _curve_sums(scored, y, curve_kw, from_logits=tiled_kw is None and not tta)
             curve_sums = part if curve_sums is None else curve_sums + part
         masked = scored                                      # what the mask-level scores (surface, instances) look at
-        if cleanup is not None:
-            masked = _one_hot_maps(_cleaned(torch.argmax(scored, dim=1), cleanup, scored.shape[1]), scored.shape[1])
+        if clean:
+            masked = _one_hot_maps(_cleaned(torch.argmax(scored, dim=1), cleanup, scored.shape[1], components), scored.shape[1])
             for cm in metrics.seg_confusion_per_image(masked, y).cpu().numpy():
                 m = metrics.metrics_from_confusion(cm)
                 miou_clean.append(m["miou"]); mdice_clean.append(m["mdice"])
@@ -311,7 +323,7 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
             miou.append(m["miou"]); mdice.append(m["mdice"]); acc.append(m["acc"])
     out = {"mIoU(%)": float(np.mean(miou) * 100), "mDice(%)": float(np.mean(mdice) * 100), "Accuracy(%)": float(np.mean(acc) * 100),
            "images": len(acc)}
-    if cleanup is not None:
+    if clean:
         out["mIoU_clean(%)"], out["mDice_clean(%)"] = float(np.mean(miou_clean) * 100), float(np.mean(mdice_clean) * 100)
     if surf_kw is not None:
         tot = torch.stack(surf_sums).sum(dim=0).cpu().tolist() if surf_sums else [0.0] * 4
@@ -354,24 +366,29 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
 
 @torch.no_grad()
 def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, tiled=None, min_area: int = 1, connectivity: int = 8,
-                      max_instances: int = 256, cleanup=None):
+                      max_instances: int = 256, cleanup=None, components=None):
     """Defects instead of pixels: instances.label_instances on the main head's arg-max mask, with maps = (confidence, uncertainty).
     The confidence is the main head's largest softmax; with tta (True, or a tuple of scales) mask and confidence are those of
     tta.predict_tta.  The uncertainty is consistency.uncertainty_map(main, aux1) of the plain forward where the model has an auxiliary
     head; a one-head model gets the confidence alone.  tiled (True, or a dict of tiled.predict_tiled keywords): mask, confidence and
     the blended per-tile uncertainty of sliding-window inference, for images of any size.  cleanup (a morphology.morphology `steps`
-    sequence): the arg-max mask goes through that chain before it is labelled, under all three paths; the maps are untouched.  Returns an
+    sequence): the arg-max mask goes through that chain before it is labelled, under all three paths; the maps are untouched.
+    components (a components.components `steps` sequence): likewise, after the cleanup chain where one is given.  Returns an
     instances.InstanceResult (records() lists the defects)."""
     from . import instances
+    clean = cleanup is not None or components is not None
+    if components is not None:
+        from .components import check_steps as check_component_steps
+        components = check_component_steps(components)
     if tiled:
         from .tiled import predict_tiled
         # (the class count of the clean-up is the blended maps' channel count: they are asked for beside the mask then)
-        kw = {**_tiled_kwargs(tiled, tta, "predict_instances"), "want": ("mask", "conf") + (("probs",) if cleanup is not None else ())}
+        kw = {**_tiled_kwargs(tiled, tta, "predict_instances"), "want": ("mask", "conf") + (("probs",) if clean else ())}
         kw.setdefault("uncertainty", "auto")
         r = predict_tiled(model, images, **kw)
         mask = r.mask
-        if cleanup is not None:
-            mask = _cleaned(mask, cleanup, r.probs.shape[1])
+        if clean:
+            mask = _cleaned(mask, cleanup, r.probs.shape[1], components)
         return instances.label_instances(mask, (r.conf,) + tuple(r.maps), connectivity=connectivity, min_area=min_area,
                                          max_instances=max_instances)
     mask, heads = predict(model, images)
@@ -382,8 +399,8 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     else:
         conf = torch.softmax(heads[0], dim=1).amax(dim=1)
     maps = (conf,) if len(heads) < 2 else (conf, consistency.uncertainty_map(heads[0], heads[1]))
-    if cleanup is not None:
-        mask = _cleaned(mask, cleanup, heads[0].shape[1])
+    if clean:
+        mask = _cleaned(mask, cleanup, heads[0].shape[1], components)
     return instances.label_instances(mask, maps, connectivity=connectivity, min_area=min_area, max_instances=max_instances)
 
 

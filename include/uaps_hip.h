@@ -1437,6 +1437,44 @@ int uaps_components_workspace_bytes(int B, int H, int W, int n_classes, size_t* 
 int uaps_components(const uaps_components_call* call);
 
 /* ---------------------------------------------------------------------------------------------
+ * Defect shape descriptors: csrc/shapes.hip.
+ *
+ * uaps_shape_descriptors: raw moments, Gray's bit-quad counts and the statistics of an optional plane, per component of the
+ *   `labels` of uaps_label_instances.  labels int32 [B, H, W]: 0 = no component, k >= 1 = component k of that image.
+ *     table int64 [B, max_instances, 11]   row k - 1 of image b describes the pixels of image b whose label is k, 1 <= k <= max_instances:
+ *       0..4  sy, sx, syy, sxy, sxx   the sums of y, x, y * y, x * y, x * x over the component's pixels (row y, column x, absolute)
+ *       5..8  q1, q2, q3, qd          bit-quad counts over the (H + 1) x (W + 1) windows {(i-1, j-1), (i-1, j), (i, j-1), (i, j)},
+ *                                     0 <= i <= H, 0 <= j <= W, pixels outside the image belonging to no component: with n the
+ *                                     number of window pixels labelled k, n = 1 adds to q1, n = 2 to q2 (the two share an edge) or qd
+ *                                     (they are diagonal), n = 3 to q3, n = 4 to nothing
+ *       9..10 pmax, psum              the maximum and the sum of max(plane, 0) over the component; plane int32 [B, H, W], or NULL:
+ *                                     both stay 0
+ *     A label <= 0 or above max_instances has no row, and counts as "not k" for every other component.  Rows without a component
+ *     are zero: the call zeroes the whole table itself.  All columns are exact integers below 2^59.
+ *   One zeroing launch and one pass over labels (and plane).  A wave owns 64 consecutive pixels of a row and reads rows y - 1, y,
+ *   y + 1; every (window, component) pair is counted by the first pixel of the window, in raster order, that carries the label; all
+ *   columns are reduced over runs of equal labels along the row.  Up to UAPS_SHAPE_LDS_ROWS rows a workgroup (rows of one image)
+ *   adds its runs into a copy of the image's table in LDS and sends the non-zero words with 64-bit atomics; above that the runs' first
+ *   lanes send them directly.  Integer atomics only: the same bits from run to run and from either form.  No workspace; the call
+ *   does not synchronise.
+ * Errors (nothing launched): UAPS_EINVAL null struct, labels or table, table == labels, non-positive dimension, max_instances < 1,
+ *   struct_size below this version's; UAPS_ERANGE H or W above UAPS_SHAPE_MAX_EXTENT, H * W >= 2^31, B * H * W * 8 >= 2 GiB, a
+ *   table of 2 GiB or more (by dimensions).
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_SHAPE_COLUMNS 11
+#define UAPS_SHAPE_MAX_EXTENT 16384
+#define UAPS_SHAPE_LDS_ROWS 256                  /* max_instances up to which a workgroup combines its runs in LDS */
+typedef struct uaps_shape_call {
+    uint32_t struct_size;
+    int32_t B, H, W, max_instances;
+    const int32_t* labels;                       /* [B][H][W] */
+    const int32_t* plane;                        /* [B][H][W] or NULL */
+    int64_t* table;                              /* [B][max_instances][11], written whole */
+    uaps_stream_t stream;
+} uaps_shape_call;
+int uaps_shape_descriptors(const uaps_shape_call* call);
+
+/* ---------------------------------------------------------------------------------------------
  * Tiled (sliding-window) full-resolution inference: csrc/tiled.hip.  An image of any size is cut into overlapping tiles of the size
  * the network runs at, the network runs on the tiles, and the tiles' probability maps are blended under a separable window.
  *

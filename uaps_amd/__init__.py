@@ -45,6 +45,10 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   components                                        component clean-up on a label map: a chain of area_open / clear_border /
                                                     fill_holes steps on the union-find kernels of label_instances;
                                                     inference.predict_instances(..., components=steps), inference.evaluate(..., components=steps)
+  shape_descriptors, ShapeResult, SHAPE_COLUMNS     defect shape descriptors from the labels of label_instances: exact moments, bit-quad
+                                                    counts and the statistics of a plane per defect in one pass; ShapeResult.props():
+                                                    centroid, axes, orientation, perimeter, compactness, holes, inradius;
+                                                    inference.predict_instances(..., shapes=True or "thickness")
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -80,6 +84,8 @@ from .curves import score_curves, plane_curves, CurveResult, CurveSums
 from . import curves
 from .morphology import morphology          # (the function takes the submodule's name: uaps_amd.morphology(mask, steps, C))
 from .components import components          # (likewise: uaps_amd.components(mask, steps, C))
+from .shapes import shape_descriptors, ShapeResult, SHAPE_COLUMNS
+from . import shapes
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -176,6 +176,7 @@ SIGNATURES = {
     "uaps_morph_band_rows": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)]),
     "uaps_components_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
     "uaps_components": (C.c_int, [_PTR]),
+    "uaps_shape_descriptors": (C.c_int, [_PTR]),
     "uaps_tile_origins": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     "uaps_tile_cut": (C.c_int, [_PTR]),
     "uaps_tile_fold": (C.c_int, [_PTR]),
@@ -388,6 +389,15 @@ class ComponentsCall(C.Structure):
                 ("classes", C.c_int32 * COMP_MAX_CLASSES), ("background", C.c_int32), ("connectivity", C.c_int32),
                 ("mask", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
                 ("stream", C.c_void_p)]
+
+
+SHAPE_COLUMNS, SHAPE_MAX_EXTENT, SHAPE_LDS_ROWS = 11, 16384, 256      # UAPS_SHAPE_COLUMNS, UAPS_SHAPE_MAX_EXTENT, UAPS_SHAPE_LDS_ROWS
+
+
+class ShapeCall(C.Structure):
+    """uaps_shape_call (include/uaps_hip.h): every operand of uaps_shape_descriptors, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("max_instances", C.c_int32),
+                ("labels", C.c_void_p), ("plane", C.c_void_p), ("table", C.c_void_p), ("stream", C.c_void_p)]
 
 
 TILE_MAX_CHUNKS, TILE_MAX_MAPS = 32, 2  # UAPS_TILE_MAX_CHUNKS, UAPS_TILE_MAX_MAPS

@@ -364,9 +364,17 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     return out
 
 
+def _with_shapes(inst, shapes, connectivity: int):
+    """predict_instances' result: the InstanceResult itself, or with `shapes` the ShapeResult that describes it."""
+    if not shapes:
+        return inst
+    from .shapes import shape_descriptors
+    return shape_descriptors(inst, thickness=shapes == "thickness", connectivity=connectivity)
+
+
 @torch.no_grad()
 def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, tiled=None, min_area: int = 1, connectivity: int = 8,
-                      max_instances: int = 256, cleanup=None, components=None):
+                      max_instances: int = 256, cleanup=None, components=None, shapes=False):
     """Defects instead of pixels: instances.label_instances on the main head's arg-max mask, with maps = (confidence, uncertainty).
     The confidence is the main head's largest softmax; with tta (True, or a tuple of scales) mask and confidence are those of
     tta.predict_tta.  The uncertainty is consistency.uncertainty_map(main, aux1) of the plain forward where the model has an auxiliary
@@ -374,8 +382,13 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     the blended per-tile uncertainty of sliding-window inference, for images of any size.  cleanup (a morphology.morphology `steps`
     sequence): the arg-max mask goes through that chain before it is labelled, under all three paths; the maps are untouched.
     components (a components.components `steps` sequence): likewise, after the cleanup chain where one is given.  Returns an
-    instances.InstanceResult (records() lists the defects)."""
+    instances.InstanceResult (records() lists the defects).
+    shapes=True, or "thickness": a shapes.ShapeResult instead -- shapes.shape_descriptors of that InstanceResult (with thickness=True
+    for "thickness"), which `.instances` holds; its props() and records() add centroid, axes, orientation, perimeter, holes and the
+    like to every defect.  Under all three paths, after the clean-up chains."""
     from . import instances
+    if shapes not in (False, True, "thickness"):
+        raise ValueError("predict_instances: shapes is False, True or \"thickness\"")
     clean = cleanup is not None or components is not None
     if components is not None:
         from .components import check_steps as check_component_steps
@@ -389,8 +402,8 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
         mask = r.mask
         if clean:
             mask = _cleaned(mask, cleanup, r.probs.shape[1], components)
-        return instances.label_instances(mask, (r.conf,) + tuple(r.maps), connectivity=connectivity, min_area=min_area,
-                                         max_instances=max_instances)
+        return _with_shapes(instances.label_instances(mask, (r.conf,) + tuple(r.maps), connectivity=connectivity, min_area=min_area,
+                                                      max_instances=max_instances), shapes, connectivity)
     mask, heads = predict(model, images)
     if tta:
         from .tta import DEFAULT_SCALES, predict_tta
@@ -401,7 +414,8 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     maps = (conf,) if len(heads) < 2 else (conf, consistency.uncertainty_map(heads[0], heads[1]))
     if clean:
         mask = _cleaned(mask, cleanup, heads[0].shape[1], components)
-    return instances.label_instances(mask, maps, connectivity=connectivity, min_area=min_area, max_instances=max_instances)
+    return _with_shapes(instances.label_instances(mask, maps, connectivity=connectivity, min_area=min_area, max_instances=max_instances),
+                        shapes, connectivity)
 
 
 def load_for_inference(model: torch.nn.Module, checkpoint_path: str, device: Optional[torch.device] = None) -> Dict:

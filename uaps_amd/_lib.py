@@ -641,6 +641,40 @@ class device_guard:
         return False
 
 
+def workspace_bytes(name: str, *dims) -> int:
+    """What the size query `name` (a uaps_*_workspace_bytes entry point) answers for `dims`."""
+    need = C.c_size_t()
+    check(getattr(lib(), name)(*dims, C.byref(need)), name)
+    return need.value
+
+
+def _fill(array, values) -> None:
+    for i, v in enumerate(values):
+        if isinstance(v, (list, tuple)):
+            _fill(array[i], v)
+        else:
+            array[i] = v
+
+
+def call(name: str, struct, device, workspace: Workspace = None, nbytes: int = 0, **fields) -> None:
+    """One call of the entry point `name`, which takes a size-versioned struct (the *_call records of include/uaps_hip.h): builds a
+    `struct`, sets struct_size, the given fields (a list or tuple fills an array field from its start), with `workspace` (the calling
+    module's own) its buffer of at least `nbytes` on the current stream, and the stream; runs under device_guard and checks the code."""
+    c = struct()
+    c.struct_size = C.sizeof(struct)
+    for k, v in fields.items():
+        if isinstance(v, (list, tuple)):
+            _fill(getattr(c, k), v)
+        else:
+            setattr(c, k, v)
+    with device_guard(device):
+        if workspace is not None:
+            ws = workspace.get(device, nbytes)
+            c.workspace, c.workspace_bytes = ws.data_ptr(), ws.numel()
+        c.stream = current_stream(device)
+        check(getattr(lib(), name)(C.byref(c)), name)
+
+
 def require_device(t, what: str):
     """The kernels only exist for the GPU: refuse CPU tensors loudly instead of computing elsewhere."""
     if not t.is_cuda:

@@ -19,26 +19,18 @@ CPU tensors take the numpy restatement below (on instances._label_image's union-
 device a missing kernel is an error."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._checks import TOO_BIG as _TOO_BIG, check_classes
 from .instances import _label_image
 
 KINDS = tuple(_lib.COMP_KINDS)
 MAX_STEPS, MAX_CLASSES = _lib.COMP_MAX_STEPS, _lib.COMP_MAX_CLASSES
-_TOO_BIG = 2 ** 31
-_ws = None
-
-
-def _workspace():
-    global _ws
-    if _ws is None:
-        _ws = _lib.Workspace()
-    return _ws
+_ws = _lib.Workspace()
 
 
 def _is_int(v) -> bool:
@@ -76,17 +68,6 @@ def check_steps(steps) -> Tuple[tuple, ...]:
             raise ValueError(f"components: n of {kind} is an integer >= 1" + (" or None" if kind == "fill_holes" else ""))
         out.append((kind, int(n)))
     return tuple(out)
-
-
-def _check_classes(classes, num_classes: int, background: int) -> Tuple[int, ...]:
-    if classes is None:
-        classes = [c for c in range(num_classes) if c != background]
-    classes = tuple(int(c) for c in classes)
-    if not 1 <= len(classes) <= MAX_CLASSES or len(set(classes)) != len(classes):
-        raise ValueError(f"components: 1..{MAX_CLASSES} distinct classes")
-    if any(c < 0 or c >= num_classes or c == background for c in classes):
-        raise ValueError("components: classes lie in [0, num_classes) and differ from the background")
-    return classes
 
 
 def _plane_words(plane: np.ndarray, conn8: bool):
@@ -157,7 +138,7 @@ def components(mask: torch.Tensor, steps, num_classes: int, *, classes: Optional
         raise ValueError(f"components: num_classes in 1..{_lib.SEG_MAX_CLASSES}")
     if not -2 ** 31 <= background < 2 ** 31:
         raise ValueError("components: the background is a 32-bit value")
-    classes = _check_classes(classes, num_classes, background)
+    classes = check_classes("components", classes, num_classes, background, MAX_CLASSES)
     if connectivity not in (4, 8):
         raise ValueError("components: connectivity is 4 or 8")
     B, H, W = mask.shape
@@ -170,24 +151,10 @@ def components(mask: torch.Tensor, steps, num_classes: int, *, classes: Optional
         return _components_cpu(mask.detach().contiguous(), steps, classes, background, int(connectivity))
     dev = mask.device
     mask = mask.detach().contiguous()
-    lib = _lib.lib()
-    need = C.c_size_t()
-    _lib.check(lib.uaps_components_workspace_bytes(B, H, W, planes, C.byref(need)), "uaps_components_workspace_bytes")
-    with _lib.device_guard(dev):
-        out = torch.empty_like(mask)
-        ws = _workspace().get(dev, need.value)
-        call = _lib.ComponentsCall()
-        call.struct_size = C.sizeof(_lib.ComponentsCall)
-        call.B, call.H, call.W, call.n_steps = B, H, W, len(steps)
-        for k, s in enumerate(steps):
-            call.kind[k] = _lib.COMP_KINDS[s[0]]
-            call.n[k] = 0 if len(s) == 1 else (_lib.COMP_ALL if s[1] is None else min(s[1], _lib.COMP_ALL))
-        call.n_classes = len(classes)
-        for k, c in enumerate(classes):
-            call.classes[k] = c
-        call.background, call.connectivity = background, int(connectivity)
-        call.mask, call.out = mask.data_ptr(), out.data_ptr()
-        call.workspace, call.workspace_bytes = ws.data_ptr(), ws.numel()
-        call.stream = _lib.current_stream(dev)
-        _lib.check(lib.uaps_components(C.byref(call)), "uaps_components")
+    out = torch.empty_like(mask)
+    _lib.call("uaps_components", _lib.ComponentsCall, dev, _ws, _lib.workspace_bytes("uaps_components_workspace_bytes", B, H, W, planes),
+              B=B, H=H, W=W, n_steps=len(steps), kind=[_lib.COMP_KINDS[s[0]] for s in steps],
+              n=[0 if len(s) == 1 else (_lib.COMP_ALL if s[1] is None else min(s[1], _lib.COMP_ALL)) for s in steps],
+              n_classes=len(classes), classes=classes, background=background, connectivity=int(connectivity),
+              mask=mask.data_ptr(), out=out.data_ptr())
     return out

@@ -14,38 +14,18 @@ bin(s) = clamp(floor((s - lo) * inv), 0, bins - 1), every step rounded in fp32, 
 CPU tensors take the numpy restatement below, as in the other modules; on a ROCm device a missing kernel is an error."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._checks import LABEL_DTYPE_CODE as _DTYPE_CODE, TOO_BIG as _TOO_BIG, as_labels
 from .instances import FIXED_ONE, InstanceResult, fixed_point
 
 MAX_BINS = _lib.CURVES_MAX_BINS
 MAX_CLASSES = 8                          # UAPS_MAX_CLASSES
-_DTYPE_CODE = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}       # UAPS_LABEL_*
-_TOO_BIG = 2 ** 31
-_ws = None
-
-
-def _workspace():
-    global _ws
-    if _ws is None:
-        _ws = _lib.Workspace()
-    return _ws
-
-
-def _as_labels(t: torch.Tensor) -> torch.Tensor:
-    """uint8, int32 and int64 travel as they are; bool and the other integer types are widened first."""
-    if t.dtype in _DTYPE_CODE:
-        return t
-    if t.dtype == torch.bool:
-        return t.to(torch.uint8)
-    if t.dtype in (torch.int8, torch.int16):
-        return t.to(torch.int32)
-    raise TypeError(f"an integer or bool tensor expected, got {t.dtype}")
+_ws = _lib.Workspace()
 
 
 def bin_factor(bins: int, lo: float, hi: float) -> np.float32:
@@ -400,7 +380,7 @@ def score_curves(scores: torch.Tensor, target: torch.Tensor, *, classes: Optiona
         raise ValueError(f"score_curves: scores {tuple(scores.shape)}, target {tuple(target.shape)}")
     if target.device != scores.device:
         raise ValueError(f"score_curves: scores are on {scores.device}, target on {target.device}")
-    target = _as_labels(target)
+    target = as_labels(target)
     if not 1 <= Cn <= MAX_CLASSES:
         raise ValueError(f"score_curves: 1 <= C <= {MAX_CLASSES}")
     if min(B, H, W) < 1:
@@ -439,35 +419,22 @@ def score_curves(scores: torch.Tensor, target: torch.Tensor, *, classes: Optiona
         return CurveResult(torch.from_numpy(hist), None if qsum is None else torch.from_numpy(qsum), torch.from_numpy(nan), pro, n_reg,
                            valid, *meta)
     scores, target = scores.detach().contiguous(), target.contiguous()
-    lib = _lib.lib()
-    need = C.c_size_t(0)
+    hist = torch.empty((B, R, 2, bins), dtype=torch.int64, device=dev)
+    qsum = torch.empty((B, R, 2, bins), dtype=torch.int64, device=dev) if want_sums else None
+    nan = torch.empty((B, R), dtype=torch.int64, device=dev)
+    pro = n_reg = None
+    fields, ws, need = {}, None, 0                         # (the workspace holds the region histograms: none without regions)
     if regions is not None:
-        _lib.check(lib.uaps_curves_workspace_bytes(B, Mg, bins, C.byref(need)), "uaps_curves_workspace_bytes")
-    with _lib.device_guard(dev):
-        hist = torch.empty((B, R, 2, bins), dtype=torch.int64, device=dev)
-        qsum = torch.empty((B, R, 2, bins), dtype=torch.int64, device=dev) if want_sums else None
-        nan = torch.empty((B, R), dtype=torch.int64, device=dev)
-        call = _lib.CurvesCall()
-        call.struct_size = C.sizeof(_lib.CurvesCall)
-        call.B, call.C, call.H, call.W, call.bins = B, Cn, H, W, bins
-        call.from_logits, call.top_row, call.n_classes = (1 if from_logits else 0), (1 if top else 0), K
-        for k, c in enumerate(classes):
-            call.classes[k] = c
-        call.target_dtype, call.lo, call.hi = _DTYPE_CODE[target.dtype], lo, hi
-        call.scores, call.target = scores.data_ptr(), target.data_ptr()
-        call.hist, call.qsum, call.nan = hist.data_ptr(), (qsum.data_ptr() if want_sums else None), nan.data_ptr()
-        pro = n_reg = None
-        held = []
-        if regions is not None:
-            held = [t.contiguous() for t in (regions.labels, regions.count, regions.table)]
-            pro = torch.empty((B, K, bins), dtype=torch.float64, device=dev)
-            n_reg = torch.empty((B, K), dtype=torch.int64, device=dev)
-            ws = _workspace().get(dev, need.value)
-            call.region_labels, call.region_count, call.region_table = [t.data_ptr() for t in held]
-            call.max_regions, call.pro_sum, call.n_regions = Mg, pro.data_ptr(), n_reg.data_ptr()
-            call.workspace, call.workspace_bytes = ws.data_ptr(), ws.numel()
-        call.stream = _lib.current_stream(dev)
-        _lib.check(lib.uaps_score_curves(C.byref(call)), "uaps_score_curves")
+        held = [t.contiguous() for t in (regions.labels, regions.count, regions.table)]
+        pro = torch.empty((B, K, bins), dtype=torch.float64, device=dev)
+        n_reg = torch.empty((B, K), dtype=torch.int64, device=dev)
+        fields = dict(region_labels=held[0].data_ptr(), region_count=held[1].data_ptr(), region_table=held[2].data_ptr(), max_regions=Mg,
+                      pro_sum=pro.data_ptr(), n_regions=n_reg.data_ptr())
+        ws, need = _ws, _lib.workspace_bytes("uaps_curves_workspace_bytes", B, Mg, bins)
+    _lib.call("uaps_score_curves", _lib.CurvesCall, dev, ws, need, B=B, C=Cn, H=H, W=W, bins=bins, from_logits=1 if from_logits else 0,
+              top_row=1 if top else 0, n_classes=K, classes=classes, target_dtype=_DTYPE_CODE[target.dtype], lo=lo, hi=hi,
+              scores=scores.data_ptr(), target=target.data_ptr(), hist=hist.data_ptr(), qsum=qsum.data_ptr() if want_sums else None,
+              nan=nan.data_ptr(), **fields)
     return CurveResult(hist, qsum, nan, pro, n_reg, valid, *meta)
 
 
@@ -483,7 +450,7 @@ def plane_curves(score: torch.Tensor, pred: torch.Tensor, target: torch.Tensor, 
             raise ValueError(f"plane_curves: score {tuple(score.shape)}, {what} {tuple(t.shape)}")
         if t.device != score.device:
             raise ValueError(f"plane_curves: score is on {score.device}, {what} on {t.device}")
-    pred, target = _as_labels(pred), _as_labels(target)
+    pred, target = as_labels(pred), as_labels(target)
     if min(B, H, W) < 1:
         raise ValueError("plane_curves: an empty tensor")
     bins, lo, hi = _check_bins("plane_curves", bins, lo, hi)
@@ -498,17 +465,10 @@ def plane_curves(score: torch.Tensor, pred: torch.Tensor, target: torch.Tensor, 
         return CurveResult(torch.from_numpy(hist), None if qsum is None else torch.from_numpy(qsum), torch.from_numpy(nan), None, None,
                            valid, *meta)
     score, pred, target = score.detach().contiguous(), pred.contiguous(), target.contiguous()
-    lib = _lib.lib()
-    with _lib.device_guard(dev):
-        hist = torch.empty((B, 1, 2, bins), dtype=torch.int64, device=dev)
-        qsum = torch.empty((B, 1, 2, bins), dtype=torch.int64, device=dev) if want_sums else None
-        nan = torch.empty((B, 1), dtype=torch.int64, device=dev)
-        call = _lib.PlaneCurvesCall()
-        call.struct_size = C.sizeof(_lib.PlaneCurvesCall)
-        call.B, call.H, call.W, call.bins, call.from_logits = B, H, W, bins, 0
-        call.pred_dtype, call.target_dtype, call.lo, call.hi = _DTYPE_CODE[pred.dtype], _DTYPE_CODE[target.dtype], lo, hi
-        call.score, call.pred, call.target = score.data_ptr(), pred.data_ptr(), target.data_ptr()
-        call.hist, call.qsum, call.nan = hist.data_ptr(), (qsum.data_ptr() if want_sums else None), nan.data_ptr()
-        call.stream = _lib.current_stream(dev)
-        _lib.check(lib.uaps_plane_curves(C.byref(call)), "uaps_plane_curves")
+    hist = torch.empty((B, 1, 2, bins), dtype=torch.int64, device=dev)
+    qsum = torch.empty((B, 1, 2, bins), dtype=torch.int64, device=dev) if want_sums else None
+    nan = torch.empty((B, 1), dtype=torch.int64, device=dev)
+    _lib.call("uaps_plane_curves", _lib.PlaneCurvesCall, dev, B=B, H=H, W=W, bins=bins, from_logits=0, pred_dtype=_DTYPE_CODE[pred.dtype],
+              target_dtype=_DTYPE_CODE[target.dtype], lo=lo, hi=hi, score=score.data_ptr(), pred=pred.data_ptr(), target=target.data_ptr(),
+              hist=hist.data_ptr(), qsum=qsum.data_ptr() if want_sums else None, nan=nan.data_ptr())
     return CurveResult(hist, qsum, nan, None, None, valid, *meta)

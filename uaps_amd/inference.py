@@ -4,12 +4,11 @@ per-image score table.  Everything runs on the HIP kernels of this package; noth
 from __future__ import annotations
 
 import operator
-from typing import Dict, Iterable, Optional, Tuple
+from typing import Dict, Iterable, NamedTuple, Optional, Tuple
 
-import numpy as np
 import torch
 
-from . import consistency, losses, metrics
+from . import consistency, losses, scoring
 
 
 @torch.no_grad()
@@ -151,49 +150,33 @@ def _tiled_kwargs(tiled, tta, what):
     return dict(tiled)
 
 
-def _surface_kwargs(surface):
-    """The keywords of a `surface` argument (True: the defaults)."""
-    if surface is True:
-        return {}
-    if not isinstance(surface, dict) or set(surface) - {"percentile", "tolerance", "classes"}:
-        raise TypeError("evaluate: surface is True or a dict with the keywords percentile, tolerance and classes")
-    return dict(surface)
+class _Forward(NamedTuple):
+    """scored: fp32 [B,C,H,W] -- the main head's logits (is_logits) or the probability maps of tta / tiled; mask: the arg-max;
+    conf: the largest probability; maps: the blended per-tile maps of the tiled path; heads: the raw heads where the plain forward
+    ran.  None for what was not asked for."""
+    scored: Optional[torch.Tensor]
+    is_logits: bool
+    mask: Optional[torch.Tensor]
+    conf: Optional[torch.Tensor]
+    maps: Tuple[torch.Tensor, ...]
+    heads: Optional[Tuple[torch.Tensor, ...]]
 
 
-def _surface_sums(scored: torch.Tensor, y: torch.Tensor, kw) -> torch.Tensor:
-    """float64 [4] on the device: the sums of hd95, assd and nsd (0 without a tolerance) over the valid pairs of the chosen classes
-    (default 1 .. C-1) of one batch, and their number."""
-    from .surface import surface_distances
-    Cn = scored.shape[1]
-    r = surface_distances(scored.float(), y, Cn, percentile=kw.get("percentile", 95.0), tolerance=kw.get("tolerance"))
-    classes = list(range(1, Cn)) if kw.get("classes") is None else [int(c) for c in kw["classes"]]
-    ok = r.valid[:, classes]
-    total = lambda v: torch.where(ok, v[:, classes], torch.zeros_like(v[:, classes])).sum()
-    nsd = total(r.nsd) if r.tolerance is not None else torch.zeros((), dtype=torch.float64, device=ok.device)
-    return torch.stack([total(r.hd95), total(r.assd), nsd, ok.sum().to(torch.float64)])
-
-
-_INSTANCE_KEYS = {"iou_threshold", "min_area", "connectivity", "max_instances", "classes"}
-
-
-def _instances_kwargs(instances):
-    """The keywords of an `instances` argument (True: the defaults)."""
-    if instances is True:
-        return {}
-    if not isinstance(instances, dict) or set(instances) - _INSTANCE_KEYS:
-        raise TypeError("evaluate: instances is True or a dict with the keywords " + ", ".join(sorted(_INSTANCE_KEYS)))
-    return dict(instances)
-
-
-def _instance_sums(scored: torch.Tensor, y: torch.Tensor, kw) -> torch.Tensor:
-    """float64 [K,7] on the device: matching.MatchResult.sums of one batch -- the defects of the arg-max of `scored` against the
-    defects of `y`, over the chosen classes (default 1 .. C-1)."""
-    from .instances import label_instances
-    from .matching import match_instances
-    lab = {k: kw[k] for k in ("min_area", "connectivity", "max_instances") if k in kw}
-    pred = label_instances(torch.argmax(scored, dim=1), **lab)
-    target = label_instances(y.to(torch.int64), **lab)
-    return match_instances(pred, target, scored.shape[1], iou_threshold=kw.get("iou_threshold", 0.5)).sums(kw.get("classes"))
+def _forward(model, images, tta, tiled_kw, want) -> _Forward:
+    """One forward down the tiled path (tiled_kw: the checked keywords, or None), the tta path (True, or a tuple of scales) or the
+    plain one.  want: among "probs" (-> scored), "mask" and "conf", and "heads": the plain predict() as well under tta."""
+    maps = tuple(k for k in want if k != "heads")
+    if tiled_kw is not None:
+        from .tiled import predict_tiled
+        r = predict_tiled(model, images, **{**tiled_kw, "want": maps})
+        return _Forward(r.probs, False, r.mask, r.conf, tuple(r.maps), None)
+    mask, heads = predict(model, images) if not tta or "heads" in want else (None, None)
+    if tta:
+        from .tta import DEFAULT_SCALES, predict_tta
+        r = predict_tta(model, images, scales=DEFAULT_SCALES if tta is True else tuple(tta), want=maps)
+        return _Forward(r.probs, False, r.mask, r.conf, (), heads)
+    conf = torch.softmax(heads[0], dim=1).amax(dim=1) if "conf" in want else None
+    return _Forward(heads[0], True, mask, conf, (), heads)
 
 
 def _cleaned(mask: torch.Tensor, cleanup, num_classes: int, components=None) -> torch.Tensor:
@@ -213,70 +196,19 @@ def _one_hot_maps(mask: torch.Tensor, num_classes: int) -> torch.Tensor:
     return torch.nn.functional.one_hot(mask, num_classes).permute(0, 3, 1, 2).contiguous().float()
 
 
-_CURVE_KEYS = {"bins", "fpr_limit", "ece_bins", "classes", "max_instances", "connectivity", "min_area", "uncertainty", "lo", "hi"}
-
-
-def _curves_kwargs(curves, tta, tiled):
-    """The keywords of a `curves` argument (True: the defaults)."""
-    if curves is True:
-        return {}
-    if not isinstance(curves, dict) or set(curves) - _CURVE_KEYS:
-        raise TypeError("evaluate: curves is True or a dict with the keywords " + ", ".join(sorted(_CURVE_KEYS)))
-    if curves.get("uncertainty") and (tta or tiled):
-        raise ValueError("evaluate: curves with uncertainty=True scores the plain forward's uncertainty map: not built under tta or tiled")
-    return dict(curves)
-
-
-def _curve_sums(scored: torch.Tensor, y: torch.Tensor, kw, from_logits: bool):
-    """curves.CurveResult.sums of one batch: the class rows (default 1 .. C-1), the top row with its fixed-point sums, and the regions
-    of the labels' defects."""
-    from .curves import score_curves
-    from .instances import label_instances
-    lab = {k: kw[k] for k in ("min_area", "connectivity", "max_instances") if k in kw}
-    regions = label_instances(y.to(torch.int64), **lab)
-    return score_curves(scored.float(), y, classes=kw.get("classes"), bins=kw.get("bins", 1024), top=True, from_logits=from_logits,
-                        regions=regions, want_sums=True).sums()
-
-
-def _uncertainty_sums(heads, y: torch.Tensor, kw):
-    """The sums of curves.plane_curves on consistency.uncertainty_map(main, aux1) against "the main head's arg-max is right"."""
-    from .curves import plane_curves
-    if len(heads) < 2:
-        raise ValueError("evaluate: curves with uncertainty=True needs a model with an auxiliary head")
-    unc = consistency.uncertainty_map(heads[0], heads[1])
-    return plane_curves(unc.float(), torch.argmax(heads[0], dim=1), y, bins=kw.get("bins", 1024), lo=kw.get("lo", 0.0),
-                        hi=kw.get("hi", 1.0)).sums()
-
-
 @torch.no_grad()
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None, tiled=None,
              surface=None, instances=None, curves=None, cleanup=None, components=None) -> Dict[str, float]:
-    """The score table of notebook cell 25: mIoU, mDice and pixel accuracy of the main head computed image by image
-    (utilities/metrics.py conventions) and averaged over the images, in percent.  tta=True, or a tuple of scales: the arg-max of the
-    multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main head's.  tiled=True, or a dict of
-    tiled.predict_tiled keywords: images of any size are scored on the blended probability maps of sliding-window inference.
-    surface=True, or a dict with the keywords percentile, tolerance and classes: the boundary metrics of surface.surface_distances
-    on the same scored maps are added -- "HD95(px)" and "ASSD(px)" (and "NSD(%)" with a tolerance), the means over the valid
-    (image, class) pairs of the whole run, and "surface_pairs", their number.  The pairs are summed on the device; one copy at the end.
-    instances=True, or a dict with the keywords iou_threshold, min_area, connectivity, max_instances and classes: the defects of the
-    scored arg-max mask are matched against the defects of the labels (instances.label_instances on both, matching.match_instances)
-    and the per-defect scores are added -- "PQ(%)", "SQ(%)", "RQ(%)", "DefectPrecision(%)", "DefectRecall(%)", "PRO(%)" (the
-    overall values of matching.summarize), "defects_gt", "defects_pred" and "instance_images_skipped" (images with more defects than
-    max_instances on either side are left out).  Summed on the device; one copy at the end.
-    curves=True, or a dict (an empty one: the defaults) with the keywords bins, fpr_limit, ece_bins, classes, max_instances, connectivity, min_area, uncertainty, lo
-    and hi: the threshold-sweep scores of curves.score_curves on the scored maps (the logits of the plain path go through the kernel's
-    softmax; under tta and tiled the maps are probabilities already) are added -- "AUROC(%)", "AP(%)", "AUPRO(%)" (up to fpr_limit,
-    default 0.3, over the defects of the labels), "ECE(%)" (ece_bins groups, default 16) and "curve_images_skipped" (images with more
-    real defects than max_instances are left out).  uncertainty=True (plain path only, a model with an auxiliary head) adds
-    "UncAUROC(%)" and "AURC": how well consistency.uncertainty_map(main, aux1), binned over [lo, hi] (default 0, 1), marks the wrong
-    pixels of the main head.  Summed on the device; one copy at the end.
-    cleanup: a morphology.morphology `steps` sequence.  The surface= and instances= branches then score the cleaned arg-max of the
-    scored maps, and "mIoU_clean(%)" and "mDice_clean(%)" are added: the same per-image rule on the cleaned mask.  Every other key
-    (the curves among them: they score maps, not masks) is what it is without cleanup.
-    components: a components.components `steps` sequence (area_open / clear_border / fill_holes), applied to the arg-max mask after
-    the cleanup chain where one is given; the same branches and the same two keys then see the mask after both."""
-    miou, mdice, acc = [], [], []
-    miou_clean, mdice_clean = [], []
+    """The score table of the main head over `batches` of (images, labels): scoring.ConfusionScorer's mIoU, mDice, pixel accuracy
+    and "images", then the keys of every family that is switched on, in this order (each scorer of scoring.py documents its own).
+    tta=True, or a tuple of scales: the multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main
+    head's logits.  tiled=True, or a dict of tiled.predict_tiled keywords: images of any size are scored on the blended probability
+    maps of sliding-window inference; not together with tta.  Both are off for every falsy value.
+    cleanup: a morphology.morphology `steps` sequence; components: a components.components `steps` sequence (area_open /
+    clear_border / fill_holes), applied to the arg-max mask after the cleanup chain where one is given.  With either, surface= and
+    instances= score the cleaned mask and scoring.CleanScorer's two keys are added; every other key is what it is without them.
+    surface (scoring.SurfaceScorer), instances (scoring.InstanceScorer): True or a dict of keywords, off for every falsy value.
+    curves (scoring.CurveScorer): True or a dict of keywords -- an empty one asks for the defaults; off for None and False."""
     if cleanup is not None:
         from .morphology import check_steps
         cleanup = check_steps(cleanup)
@@ -284,83 +216,24 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         from .components import check_steps as check_component_steps
         components = check_component_steps(components)
     clean = cleanup is not None or components is not None
-    curve_kw = _curves_kwargs(curves, tta, tiled) if curves is not None and curves is not False else None      # ({}: the defaults)
-    curve_sums = unc_sums = None
+    curve = scoring.CurveScorer(curves, plain_path=not (tta or tiled)) if curves is not None and curves is not False else None
     tiled_kw = _tiled_kwargs(tiled, tta, "evaluate") if tiled else None
-    surf_kw = _surface_kwargs(surface) if surface else None
-    surf_sums = []
-    inst_kw = _instances_kwargs(instances) if instances else None
-    inst_sums = []
+    base = scoring.ConfusionScorer()
+    scorers = [base, scoring.CleanScorer() if clean else None, scoring.SurfaceScorer(surface) if surface else None,
+               scoring.InstanceScorer(instances) if instances else None, curve]
+    scorers = [s for s in scorers if s is not None]
     for x, y in batches:
-        if tiled_kw is not None:
-            from .tiled import predict_tiled
-            scored = predict_tiled(model, x, **{**tiled_kw, "want": ("probs",)}).probs
-        elif tta:
-            from .tta import DEFAULT_SCALES, predict_tta
-            scored = predict_tta(model, x, scales=DEFAULT_SCALES if tta is True else tuple(tta), want=("probs",)).probs
-        else:
-            heads = predict(model, x)[1]
-            scored = heads[0]
-            if curve_kw is not None and curve_kw.get("uncertainty"):
-                part = _uncertainty_sums(heads, y, curve_kw)
-                unc_sums = part if unc_sums is None else unc_sums + part
-        if curve_kw is not None:
-            part = _curve_sums(scored, y, curve_kw, from_logits=tiled_kw is None and not tta)
-            curve_sums = part if curve_sums is None else curve_sums + part
-        masked = scored                                      # what the mask-level scores (surface, instances) look at
+        f = _forward(model, x, tta, tiled_kw, ("probs",))
+        masked = f.scored
         if clean:
-            masked = _one_hot_maps(_cleaned(torch.argmax(scored, dim=1), cleanup, scored.shape[1], components), scored.shape[1])
-            for cm in metrics.seg_confusion_per_image(masked, y).cpu().numpy():
-                m = metrics.metrics_from_confusion(cm)
-                miou_clean.append(m["miou"]); mdice_clean.append(m["mdice"])
-        if surf_kw is not None:
-            surf_sums.append(_surface_sums(masked, y, surf_kw))
-        if inst_kw is not None:
-            inst_sums.append(_instance_sums(masked, y, inst_kw))
-        cms = metrics.seg_confusion_per_image(scored, y).cpu().numpy()
-        for cm in cms:
-            m = metrics.metrics_from_confusion(cm)
-            miou.append(m["miou"]); mdice.append(m["mdice"]); acc.append(m["acc"])
-    out = {"mIoU(%)": float(np.mean(miou) * 100), "mDice(%)": float(np.mean(mdice) * 100), "Accuracy(%)": float(np.mean(acc) * 100),
-           "images": len(acc)}
-    if clean:
-        out["mIoU_clean(%)"], out["mDice_clean(%)"] = float(np.mean(miou_clean) * 100), float(np.mean(mdice_clean) * 100)
-    if surf_kw is not None:
-        tot = torch.stack(surf_sums).sum(dim=0).cpu().tolist() if surf_sums else [0.0] * 4
-        pairs = int(tot[3])
-        mean = lambda v: v / pairs if pairs else float("nan")
-        out["HD95(px)"], out["ASSD(px)"] = mean(tot[0]), mean(tot[1])
-        if surf_kw.get("tolerance") is not None:
-            out["NSD(%)"] = mean(tot[2]) * 100
-        out["surface_pairs"] = pairs
-    if inst_kw is not None:
-        from .matching import SUM_COLUMNS, summarize
-        Cn = None if not inst_sums else inst_sums[0].shape[0]
-        classes = inst_kw.get("classes")
-        classes = list(range(1, (Cn or 0) + 1)) if classes is None else [int(c) for c in classes]
-        tot = torch.stack(inst_sums).sum(dim=0).cpu().numpy() if inst_sums else np.zeros((len(classes), len(SUM_COLUMNS)))
-        s = summarize(tot, classes, len(acc))
-        for key, name in (("PQ(%)", "PQ"), ("SQ(%)", "SQ"), ("RQ(%)", "RQ"), ("DefectPrecision(%)", "precision"),
-                          ("DefectRecall(%)", "recall"), ("PRO(%)", "PRO")):
-            out[key] = s[name] * 100
-        out["defects_gt"], out["defects_pred"], out["instance_images_skipped"] = s["n_gt"], s["n_pred"], s["images_skipped"]
-    if curve_kw is not None:
-        from .curves import summarize as curve_summarize
-        nan = float("nan")
-        s = {"AUROC": nan, "AP": nan, "AUPRO": nan, "ECE": nan, "images_skipped": 0}
-        if curve_sums is not None:
-            Cn = curve_sums.hist.shape[0]                     # the class rows and the top row
-            classes = curve_kw.get("classes")
-            classes = list(range(1, Cn)) if classes is None else [int(c) for c in classes]
-            s = curve_summarize(curve_sums, classes, fpr_limit=curve_kw.get("fpr_limit", 0.3), ece_bins=curve_kw.get("ece_bins", 16))
-        for key in ("AUROC", "AP", "AUPRO", "ECE"):
-            out[key + "(%)"] = s[key] * 100
-        out["curve_images_skipped"] = s["images_skipped"]
-        if curve_kw.get("uncertainty"):
-            u = {"AUROC": nan, "AURC": nan}
-            if unc_sums is not None:
-                u = curve_summarize(unc_sums, (), lo=curve_kw.get("lo", 0.0), hi=curve_kw.get("hi", 1.0), plane=True)
-            out["UncAUROC(%)"], out["AURC"] = u["AUROC"] * 100, u["AURC"]
+            Cn = f.scored.shape[1]
+            masked = _one_hot_maps(_cleaned(torch.argmax(f.scored, dim=1), cleanup, Cn, components), Cn)
+        batch = scoring.Batch(f.scored, f.is_logits, masked, y, f.heads)
+        for s in scorers:
+            s.update(batch)
+    out = {}
+    for s in scorers:
+        out.update(s.result(base.images))
     return out
 
 
@@ -393,27 +266,18 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     if components is not None:
         from .components import check_steps as check_component_steps
         components = check_component_steps(components)
+    tiled_kw, want = None, ("mask", "conf", "heads")
     if tiled:
-        from .tiled import predict_tiled
         # (the class count of the clean-up is the blended maps' channel count: they are asked for beside the mask then)
-        kw = {**_tiled_kwargs(tiled, tta, "predict_instances"), "want": ("mask", "conf") + (("probs",) if clean else ())}
-        kw.setdefault("uncertainty", "auto")
-        r = predict_tiled(model, images, **kw)
-        mask = r.mask
-        if clean:
-            mask = _cleaned(mask, cleanup, r.probs.shape[1], components)
-        return _with_shapes(instances.label_instances(mask, (r.conf,) + tuple(r.maps), connectivity=connectivity, min_area=min_area,
-                                                      max_instances=max_instances), shapes, connectivity)
-    mask, heads = predict(model, images)
-    if tta:
-        from .tta import DEFAULT_SCALES, predict_tta
-        r = predict_tta(model, images, scales=DEFAULT_SCALES if tta is True else tuple(tta), want=("mask", "conf"))
-        mask, conf = r.mask, r.conf
-    else:
-        conf = torch.softmax(heads[0], dim=1).amax(dim=1)
-    maps = (conf,) if len(heads) < 2 else (conf, consistency.uncertainty_map(heads[0], heads[1]))
+        tiled_kw, want = _tiled_kwargs(tiled, tta, "predict_instances"), ("mask", "conf") + (("probs",) if clean else ())
+        tiled_kw.setdefault("uncertainty", "auto")
+    f = _forward(model, images, tta, tiled_kw, want)
+    maps = (f.conf,) + f.maps
+    if f.heads is not None and len(f.heads) >= 2:
+        maps += (consistency.uncertainty_map(f.heads[0], f.heads[1]),)
+    mask = f.mask
     if clean:
-        mask = _cleaned(mask, cleanup, heads[0].shape[1], components)
+        mask = _cleaned(mask, cleanup, (f.scored if f.heads is None else f.heads[0]).shape[1], components)
     return _with_shapes(instances.label_instances(mask, maps, connectivity=connectivity, min_area=min_area, max_instances=max_instances),
                         shapes, connectivity)
 

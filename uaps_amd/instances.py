@@ -13,18 +13,17 @@ CPU tensors take the numpy restatements below (a two-pass union-find; no scipy),
 kernel is an error."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._checks import TOO_BIG as _TOO_BIG
 
 TABLE_COLUMNS = ("class", "area", "y0", "x0", "y1", "x1", "first_pixel", "sum0", "sum1")
 FIXED_ONE = 16777216.0                   # 2^24: q(v) = (int64) rint(clamp(v, -65536, 65536) * 2^24)
-_TOO_BIG = 2 ** 31
-_ws = None
+_ws = _lib.Workspace()
 
 
 class InstanceResult(NamedTuple):
@@ -67,13 +66,6 @@ class InstanceResult(NamedTuple):
                              "mean0": means[0], "mean1": means[1]})
             out.append(recs)
         return out
-
-
-def _workspace():
-    global _ws
-    if _ws is None:
-        _ws = _lib.Workspace()
-    return _ws
 
 
 def fixed_point(v: np.ndarray) -> np.ndarray:
@@ -195,26 +187,14 @@ def label_instances(mask: torch.Tensor, maps: Sequence[torch.Tensor] = (), *, co
     dev = mask.device
     mask = mask.detach().contiguous()
     maps = [t.detach().contiguous() for t in maps]
-    lib = _lib.lib()
-    need = C.c_size_t()
-    _lib.check(lib.uaps_instances_workspace_bytes(B, H, W, C.byref(need)), "uaps_instances_workspace_bytes")
-    with _lib.device_guard(dev):
-        labels = torch.empty((B, H, W), dtype=torch.int32, device=dev)
-        count = torch.empty((B,), dtype=torch.int32, device=dev)
-        table = torch.empty((B, max_instances, 9), dtype=torch.int64, device=dev)
-        ws = _workspace().get(dev, need.value)
-        call = _lib.InstancesCall()
-        call.struct_size = C.sizeof(_lib.InstancesCall)
-        call.B, call.H, call.W, call.connectivity = B, H, W, connectivity
-        call.has_background, call.background = (0, 0) if background is None else (1, int(background))
-        call.min_area, call.max_instances = min_area, max_instances
-        call.mask = mask.data_ptr()
-        call.map0 = maps[0].data_ptr() if len(maps) > 0 else None
-        call.map1 = maps[1].data_ptr() if len(maps) > 1 else None
-        call.labels, call.count, call.table = labels.data_ptr(), count.data_ptr(), table.data_ptr()
-        call.workspace, call.workspace_bytes = ws.data_ptr(), ws.numel()
-        call.stream = _lib.current_stream(dev)
-        _lib.check(lib.uaps_label_instances(C.byref(call)), "uaps_label_instances")
+    labels = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    table = torch.empty((B, max_instances, 9), dtype=torch.int64, device=dev)
+    _lib.call("uaps_label_instances", _lib.InstancesCall, dev, _ws, _lib.workspace_bytes("uaps_instances_workspace_bytes", B, H, W),
+              B=B, H=H, W=W, connectivity=connectivity, has_background=0 if background is None else 1,
+              background=0 if background is None else int(background), min_area=min_area, max_instances=max_instances,
+              mask=mask.data_ptr(), map0=maps[0].data_ptr() if len(maps) > 0 else None, map1=maps[1].data_ptr() if len(maps) > 1 else None,
+              labels=labels.data_ptr(), count=count.data_ptr(), table=table.data_ptr())
     return InstanceResult(labels, count, table, len(maps))
 
 
@@ -250,16 +230,6 @@ def _plane_runs(plane: np.ndarray) -> np.ndarray:
     return np.stack([starts + 1, ends - starts], axis=1).astype(np.int32)
 
 
-def _rle_call(B, H, W, classes, stream):
-    call = _lib.RleCall()
-    call.struct_size = C.sizeof(_lib.RleCall)
-    call.B, call.H, call.W, call.n_classes = B, H, W, len(classes)
-    for k, c in enumerate(classes):
-        call.classes[k] = c
-    call.stream = stream
-    return call
-
-
 def mask_to_rle(mask: torch.Tensor, classes: Sequence[int]) -> RLE:
     """The runs of every (image, class) of a label array [B,H,W] (int64, or the uint8 arrays the input pipelines keep).  Two passes on
     the device -- count and scan, then write -- with one host read of the total between them, which sizes `pairs`."""
@@ -279,19 +249,15 @@ def mask_to_rle(mask: torch.Tensor, classes: Sequence[int]) -> RLE:
         return RLE(torch.from_numpy(pairs), torch.from_numpy(offsets), (H, W), classes)
     dev = mask.device
     mask = mask.detach().to(torch.int64).contiguous()
-    lib = _lib.lib()
-    with _lib.device_guard(dev):
-        n = B * len(classes) * W
-        col = torch.empty((n + 1,), dtype=torch.int32, device=dev)
-        call = _rle_call(B, H, W, classes, _lib.current_stream(dev))
-        call.mask, call.col_offsets = mask.data_ptr(), col.data_ptr()
-        _lib.check(lib.uaps_rle_count(C.byref(call)), "uaps_rle_count")
-        total = int(col[n])                                 # the one synchronisation: the size of the result
-        pairs = torch.empty((total, 2), dtype=torch.int32, device=dev)
-        if total:
-            call.pairs = pairs.data_ptr()
-            _lib.check(lib.uaps_rle_encode(C.byref(call)), "uaps_rle_encode")
-        offsets = col[::W].contiguous()
+    n = B * len(classes) * W
+    col = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+    fields = dict(B=B, H=H, W=W, n_classes=len(classes), classes=classes, mask=mask.data_ptr(), col_offsets=col.data_ptr())
+    _lib.call("uaps_rle_count", _lib.RleCall, dev, **fields)
+    total = int(col[n])                                     # the one synchronisation: the size of the result
+    pairs = torch.empty((total, 2), dtype=torch.int32, device=dev)
+    if total:
+        _lib.call("uaps_rle_encode", _lib.RleCall, dev, pairs=pairs.data_ptr(), **fields)
+    offsets = col[::W].contiguous()
     return RLE(pairs, offsets, (H, W), classes)
 
 
@@ -325,12 +291,10 @@ def rle_to_mask(pairs: torch.Tensor, offsets: torch.Tensor, shape: Tuple[int, in
         return torch.from_numpy(out.reshape(B, W, H).transpose(0, 2, 1).copy()).to(dtype)
     dev = pairs.device
     pairs, offsets = pairs.contiguous(), offsets.to(dev).contiguous()
-    with _lib.device_guard(dev):
-        out = torch.empty((B, H, W), dtype=dtype, device=dev)
-        call = _rle_call(B, H, W, classes, _lib.current_stream(dev))
-        call.pairs, call.offsets, call.n_runs = (pairs.data_ptr() if pairs.shape[0] else None), offsets.data_ptr(), pairs.shape[0]
-        call.out, call.out_uint8 = out.data_ptr(), 1 if dtype == torch.uint8 else 0
-        _lib.check(_lib.lib().uaps_rle_decode(C.byref(call)), "uaps_rle_decode")
+    out = torch.empty((B, H, W), dtype=dtype, device=dev)
+    _lib.call("uaps_rle_decode", _lib.RleCall, dev, B=B, H=H, W=W, n_classes=len(classes), classes=classes,
+              pairs=pairs.data_ptr() if pairs.shape[0] else None, offsets=offsets.data_ptr(), n_runs=pairs.shape[0], out=out.data_ptr(),
+              out_uint8=1 if dtype == torch.uint8 else 0)
     return out
 
 

@@ -12,28 +12,20 @@ the device-to-host copies.
 CPU tensors take the numpy restatement below, as in the other modules; on a ROCm device a missing kernel is an error."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._checks import TOO_BIG as _TOO_BIG
 from .instances import InstanceResult
 
 MATCH_COLUMNS = ("partner", "inter", "covered", "matched")
 COUNT_COLUMNS = ("tp", "n_pred", "n_gt")
 SUM_COLUMNS = ("tp", "fp", "fn", "sum_iou", "sum_pro", "sum_purity", "images")
 MAX_CLASSES = _lib.MATCH_MAX_CLASSES
-_TOO_BIG = 2 ** 31
-_ws = None
-
-
-def _workspace():
-    global _ws
-    if _ws is None:
-        _ws = _lib.Workspace()
-    return _ws
+_ws = _lib.Workspace()
 
 
 def _ratio(num: float, den: float) -> float:
@@ -234,24 +226,13 @@ def match_instances(pred: InstanceResult, target: InstanceResult, num_classes: i
         out_p, out_g, counts = _match_cpu(pred, target, Cn, thr, bool(class_agnostic))
         return MatchResult(out_p, out_g, counts, valid, thr, pred, target)
     dev = pred.labels.device
-    tensors = [t.contiguous() for t in (pred.labels, target.labels, pred.count, target.count, pred.table, target.table)]
-    lib = _lib.lib()
-    need = C.c_size_t()
-    _lib.check(lib.uaps_match_workspace_bytes(B, Mp, Mg, C.byref(need)), "uaps_match_workspace_bytes")
-    with _lib.device_guard(dev):
-        out_p = torch.empty((B, Mp, 4), dtype=torch.int64, device=dev)
-        out_g = torch.empty((B, Mg, 4), dtype=torch.int64, device=dev)
-        counts = torch.empty((B, Cn, 3), dtype=torch.int64, device=dev)
-        ws = _workspace().get(dev, need.value)
-        call = _lib.MatchCall()
-        call.struct_size = C.sizeof(_lib.MatchCall)
-        call.B, call.H, call.W, call.num_classes, call.class_agnostic = B, H, W, Cn, 1 if class_agnostic else 0
-        call.iou_threshold = thr
-        (call.pred_labels, call.target_labels, call.pred_count, call.target_count, call.pred_table,
-         call.target_table) = [t.data_ptr() for t in tensors]
-        call.max_pred, call.max_gt = Mp, Mg
-        call.pred_out, call.target_out, call.counts = out_p.data_ptr(), out_g.data_ptr(), counts.data_ptr()
-        call.workspace, call.workspace_bytes = ws.data_ptr(), ws.numel()
-        call.stream = _lib.current_stream(dev)
-        _lib.check(lib.uaps_match_instances(C.byref(call)), "uaps_match_instances")
+    held = {side + "_" + name: getattr(r, name).contiguous() for side, r in (("pred", pred), ("target", target))
+            for name in ("labels", "count", "table")}
+    out_p = torch.empty((B, Mp, 4), dtype=torch.int64, device=dev)
+    out_g = torch.empty((B, Mg, 4), dtype=torch.int64, device=dev)
+    counts = torch.empty((B, Cn, 3), dtype=torch.int64, device=dev)
+    _lib.call("uaps_match_instances", _lib.MatchCall, dev, _ws, _lib.workspace_bytes("uaps_match_workspace_bytes", B, Mp, Mg),
+              B=B, H=H, W=W, num_classes=Cn, class_agnostic=1 if class_agnostic else 0, iou_threshold=thr, max_pred=Mp, max_gt=Mg,
+              pred_out=out_p.data_ptr(), target_out=out_g.data_ptr(), counts=counts.data_ptr(),
+              **{name: t.data_ptr() for name, t in held.items()})
     return MatchResult(out_p, out_g, counts, valid, thr, pred, target)

@@ -25,11 +25,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._checks import TOO_BIG as _TOO_BIG, check_classes
 
 OPS = tuple(_lib.MORPH_OPS)
 FOOTPRINTS = tuple(_lib.MORPH_FOOTPRINTS)
 MAX_STEPS, MAX_CLASSES, MAX_RADIUS, MAX_REACH, MAX_EXTENT = _lib.MORPH_MAX_STEPS, _lib.MORPH_MAX_CLASSES, 15, 64, 4096
-_TOO_BIG = 2 ** 31
 
 
 def half_widths(footprint: str, radius: int) -> List[int]:
@@ -130,17 +130,6 @@ def _morph_cpu(mask: torch.Tensor, steps, classes, background: int) -> torch.Ten
     return torch.from_numpy(m)
 
 
-def _check_classes(classes, num_classes: int, background: int) -> Tuple[int, ...]:
-    if classes is None:
-        classes = [c for c in range(num_classes) if c != background]
-    classes = tuple(int(c) for c in classes)
-    if not 1 <= len(classes) <= MAX_CLASSES or len(set(classes)) != len(classes):
-        raise ValueError(f"morphology: 1..{MAX_CLASSES} distinct classes")
-    if any(c < 0 or c >= num_classes or c == background for c in classes):
-        raise ValueError("morphology: classes lie in [0, num_classes) and differ from the background")
-    return classes
-
-
 def morphology(mask: torch.Tensor, steps, num_classes: int, *, classes: Optional[Sequence[int]] = None, background: int = 0,
                _band_rows: int = 0) -> torch.Tensor:
     """The chain `steps` applied to the int64 label map [B,H,W]; a new tensor.  classes: at most 8 distinct values in
@@ -154,7 +143,7 @@ def morphology(mask: torch.Tensor, steps, num_classes: int, *, classes: Optional
         raise ValueError(f"morphology: num_classes in 1..{_lib.SEG_MAX_CLASSES}")
     if not -2 ** 31 <= background < 2 ** 31:
         raise ValueError("morphology: the background is a 32-bit value")
-    classes = _check_classes(classes, num_classes, background)
+    classes = check_classes("morphology", classes, num_classes, background, MAX_CLASSES)
     B, H, W = mask.shape
     if B < 1 or H < 1 or W < 1:
         raise ValueError("morphology: empty mask")
@@ -166,20 +155,10 @@ def morphology(mask: torch.Tensor, steps, num_classes: int, *, classes: Optional
         return _morph_cpu(mask.detach().contiguous(), steps, classes, background)
     dev = mask.device
     mask = mask.detach().contiguous()
-    with _lib.device_guard(dev):
-        out = torch.empty_like(mask)
-        call = _lib.MorphCall()
-        call.struct_size = C.sizeof(_lib.MorphCall)
-        call.B, call.H, call.W, call.n_steps = B, H, W, len(steps)
-        for k, (op, fp, r) in enumerate(steps):
-            call.op[k], call.footprint[k], call.radius[k] = _lib.MORPH_OPS[op], _lib.MORPH_FOOTPRINTS[fp], r
-        call.n_classes = len(classes)
-        for k, c in enumerate(classes):
-            call.classes[k] = c
-        call.background, call.band_rows = background, int(_band_rows)
-        call.mask, call.out = mask.data_ptr(), out.data_ptr()
-        call.stream = _lib.current_stream(dev)
-        _lib.check(_lib.lib().uaps_morphology(C.byref(call)), "uaps_morphology")
+    out = torch.empty_like(mask)
+    _lib.call("uaps_morphology", _lib.MorphCall, dev, B=B, H=H, W=W, n_steps=len(steps), op=[_lib.MORPH_OPS[s[0]] for s in steps],
+              footprint=[_lib.MORPH_FOOTPRINTS[s[1]] for s in steps], radius=[s[2] for s in steps], n_classes=len(classes),
+              classes=classes, background=background, band_rows=int(_band_rows), mask=mask.data_ptr(), out=out.data_ptr())
     return out
 
 

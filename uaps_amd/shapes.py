@@ -25,7 +25,6 @@ was compared with it):
 CPU tensors take the numpy restatement below, as in the other modules; on a ROCm device a missing kernel is an error."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, List, NamedTuple, Optional
 
@@ -33,11 +32,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._checks import TOO_BIG as _TOO_BIG
 from .instances import InstanceResult
 
 SHAPE_COLUMNS = ("sy", "sx", "syy", "sxy", "sxx", "q1", "q2", "q3", "qd", "pmax", "psum")
 MAX_EXTENT = _lib.SHAPE_MAX_EXTENT
-_TOO_BIG = 2 ** 31
 assert len(SHAPE_COLUMNS) == _lib.SHAPE_COLUMNS
 
 
@@ -215,15 +214,7 @@ def shape_descriptors(inst: InstanceResult, plane: Optional[torch.Tensor] = None
         table = torch.from_numpy(_shapes_cpu(labels.numpy(), None if plane is None else plane.numpy(), M))
         return ShapeResult(table, inst, int(connectivity), kind)
     dev = labels.device
-    lib = _lib.lib()
-    with _lib.device_guard(dev):
-        table = torch.empty((B, M, 11), dtype=torch.int64, device=dev)
-        call = _lib.ShapeCall()
-        call.struct_size = C.sizeof(_lib.ShapeCall)
-        call.B, call.H, call.W, call.max_instances = B, H, W, M
-        call.labels = labels.data_ptr()
-        call.plane = None if plane is None else plane.data_ptr()
-        call.table = table.data_ptr()
-        call.stream = _lib.current_stream(dev)
-        _lib.check(lib.uaps_shape_descriptors(C.byref(call)), "uaps_shape_descriptors")
+    table = torch.empty((B, M, 11), dtype=torch.int64, device=dev)
+    _lib.call("uaps_shape_descriptors", _lib.ShapeCall, dev, B=B, H=H, W=W, max_instances=M, labels=labels.data_ptr(),
+              plane=None if plane is None else plane.data_ptr(), table=table.data_ptr())
     return ShapeResult(table, inst, int(connectivity), kind)

@@ -11,7 +11,6 @@ CPU tensors take the numpy restatements below (a separable transform with a chun
 modules; on a ROCm device a missing kernel is an error."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, NamedTuple, Optional, Sequence
 
@@ -19,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._checks import LABEL_DTYPE_CODE as _DTYPE_CODE, as_labels
 
 SURFACE_COLUMNS = ("n_pred", "n_gt", "max_pg", "max_gp", "sum16_pg", "sum16_gp", "within_pg", "within_gp", "rank_lo", "rank_hi",
                    "q_lo", "q_hi")
@@ -26,15 +26,7 @@ NO_FEATURE = 2 ** 30                     # UAPS_EDT_NO_FEATURE: distance_transfo
 MAX_EXTENT = 4096                        # UAPS_SURFACE_MAX_EXTENT
 MAX_CLASSES = 8                          # UAPS_MAX_CLASSES
 SUM_ONE = 65536.0                        # sum16 = sum of floor(2^16 sqrt(d2))
-_DTYPE_CODE = {torch.uint8: 1, torch.int32: 4, torch.int64: 8}       # UAPS_LABEL_*
-_ws = None
-
-
-def _workspace():
-    global _ws
-    if _ws is None:
-        _ws = _lib.Workspace()
-    return _ws
+_ws = _lib.Workspace()
 
 
 class SurfaceResult(NamedTuple):
@@ -191,23 +183,12 @@ def _check_extent(what: str, H: int, W: int, B: int) -> None:
         raise ValueError(f"{what}: 1 <= H, W <= {MAX_EXTENT}")
 
 
-def _as_labels(t: torch.Tensor) -> torch.Tensor:
-    """uint8, int32 and int64 travel as they are; bool and the other integer types are widened first."""
-    if t.dtype in _DTYPE_CODE:
-        return t
-    if t.dtype == torch.bool:
-        return t.to(torch.uint8)
-    if t.dtype in (torch.int8, torch.int16):
-        return t.to(torch.int32)
-    raise TypeError(f"an integer or bool tensor expected, got {t.dtype}")
-
-
 def distance_transform_sq(mask: torch.Tensor) -> torch.Tensor:
     """The exact squared Euclidean distance of every pixel of a bool or integer [H,W] or [B,H,W] mask to the nearest zero pixel, int32,
     0 at zero pixels: scipy.ndimage.distance_transform_edt(mask) squared.  An image without a zero pixel gets NO_FEATURE everywhere."""
     if mask.dim() not in (2, 3):
         raise TypeError("distance_transform_sq: [H,W] or [B,H,W] expected")
-    m = _as_labels(mask.detach())
+    m = as_labels(mask.detach())
     m3 = (m if m.dim() == 3 else m[None]).contiguous()
     B, H, W = m3.shape
     _check_extent("distance_transform_sq", H, W, B)
@@ -216,19 +197,9 @@ def distance_transform_sq(mask: torch.Tensor) -> torch.Tensor:
         out = torch.from_numpy(np.stack([_edt_sq_np(a[b] == 0) for b in range(B)]).astype(np.int32))
         return out.reshape(mask.shape)
     dev = m3.device
-    lib = _lib.lib()
-    need = C.c_size_t()
-    _lib.check(lib.uaps_edt_workspace_bytes(B, H, W, C.byref(need)), "uaps_edt_workspace_bytes")
-    with _lib.device_guard(dev):
-        out = torch.empty((B, H, W), dtype=torch.int32, device=dev)
-        ws = _workspace().get(dev, need.value)
-        call = _lib.EdtCall()
-        call.struct_size = C.sizeof(_lib.EdtCall)
-        call.B, call.H, call.W, call.mask_dtype = B, H, W, _DTYPE_CODE[m3.dtype]
-        call.mask, call.out = m3.data_ptr(), out.data_ptr()
-        call.workspace, call.workspace_bytes = ws.data_ptr(), ws.numel()
-        call.stream = _lib.current_stream(dev)
-        _lib.check(lib.uaps_edt_sq(C.byref(call)), "uaps_edt_sq")
+    out = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    _lib.call("uaps_edt_sq", _lib.EdtCall, dev, _ws, _lib.workspace_bytes("uaps_edt_workspace_bytes", B, H, W),
+              B=B, H=H, W=W, mask_dtype=_DTYPE_CODE[m3.dtype], mask=m3.data_ptr(), out=out.data_ptr())
     return out.reshape(mask.shape)
 
 
@@ -273,24 +244,10 @@ def surface_distances(pred: torch.Tensor, target: torch.Tensor, num_classes: int
         table = _surface_cpu(p.astype(np.int64), target.numpy().astype(np.int64), Cn, percentile, tol)
         return SurfaceResult(torch.from_numpy(table), percentile, tolerance)
     dev = target.device
-    lib = _lib.lib()
-    need = C.c_size_t()
-    _lib.check(lib.uaps_surface_workspace_bytes(B, Cn, H, W, C.byref(need)), "uaps_surface_workspace_bytes")
-    with _lib.device_guard(dev):
-        table = torch.empty((B, Cn, len(SURFACE_COLUMNS)), dtype=torch.int64, device=dev)
-        ws = _workspace().get(dev, need.value)
-        call = _lib.SurfaceCall()
-        call.struct_size = C.sizeof(_lib.SurfaceCall)
-        call.B, call.C, call.H, call.W = B, Cn, H, W
-        call.target_dtype, call.target = _DTYPE_CODE[target.dtype], target.data_ptr()
-        if scores:
-            call.pred, call.pred_scores, call.pred_dtype = None, pred.data_ptr(), 0
-        else:
-            call.pred, call.pred_scores, call.pred_dtype = pred.data_ptr(), None, _DTYPE_CODE[pred.dtype]
-        call.percentile_frac = percentile / 100.0
-        call.has_tolerance, call.tol_d2 = (0, 0) if tol is None else (1, tol)
-        call.table = table.data_ptr()
-        call.workspace, call.workspace_bytes = ws.data_ptr(), ws.numel()
-        call.stream = _lib.current_stream(dev)
-        _lib.check(lib.uaps_surface_distances(C.byref(call)), "uaps_surface_distances")
+    table = torch.empty((B, Cn, len(SURFACE_COLUMNS)), dtype=torch.int64, device=dev)
+    _lib.call("uaps_surface_distances", _lib.SurfaceCall, dev, _ws, _lib.workspace_bytes("uaps_surface_workspace_bytes", B, Cn, H, W),
+              B=B, C=Cn, H=H, W=W, target_dtype=_DTYPE_CODE[target.dtype], target=target.data_ptr(),
+              pred=None if scores else pred.data_ptr(), pred_scores=pred.data_ptr() if scores else None,
+              pred_dtype=0 if scores else _DTYPE_CODE[pred.dtype], percentile_frac=percentile / 100.0,
+              has_tolerance=0 if tol is None else 1, tol_d2=0 if tol is None else tol, table=table.data_ptr())
     return SurfaceResult(table, percentile, tolerance)

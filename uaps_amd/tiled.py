@@ -14,7 +14,6 @@ TTA inside tiles, a margin-crop mode, uint8 sources, a captured tile forward, ov
 of scope."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import NamedTuple, Optional, Sequence, Tuple
 
@@ -145,10 +144,8 @@ def tile_cut(x: torch.Tensor, plan: TilePlan, g0: int = 0, g1: Optional[int] = N
         return torch.stack(tiles)
     x = x.detach().contiguous()
     out = torch.empty((g1 - g0, Cin, th, tw), dtype=torch.float32, device=x.device)
-    call = _lib.TileCutCall(C.sizeof(_lib.TileCutCall), B, Cin, H, W, th, tw, oy, ox, g0, g1, x.data_ptr(), out.data_ptr(),
-                            _lib.current_stream(x.device))
-    with _lib.device_guard(x.device):
-        _lib.check(_lib.lib().uaps_tile_cut(C.byref(call)), "uaps_tile_cut")
+    _lib.call("uaps_tile_cut", _lib.TileCutCall, x.device, B=B, Cin=Cin, H=H, W=W, th=th, tw=tw, oy=oy, ox=ox, g0=g0, g1=g1,
+              x=x.data_ptr(), out=out.data_ptr())
     return out
 
 
@@ -246,25 +243,10 @@ def tile_fold(chunks, plan: TilePlan, shape, window="triangle", maps: Sequence =
     mask = torch.empty((B, H, W), dtype=torch.int64, device=dev) if "mask" in want else None
     conf = torch.empty((B, H, W), dtype=torch.float32, device=dev) if "conf" in want else None
     mout = [torch.empty((B, H, W), dtype=torch.float32, device=dev) for _ in ms]
-    call = _lib.TileFoldCall()
-    call.struct_size = C.sizeof(_lib.TileFoldCall)
-    call.B, call.C, call.H, call.W = B, Cc, H, W
-    call.th, call.tw, call.oy, call.ox = th, tw, oy, ox
-    call.n_chunks, call.tiles_per_chunk, call.n_maps = n_chunks, tpc, len(ms)
-    for k in range(n_chunks):
-        if zs is not None:
-            call.logits[k] = zs[k].data_ptr()
-        for m, cs in enumerate(ms):
-            call.maps[m][k] = cs[k].data_ptr()
-    call.wy, call.wx = wy.data_ptr(), wx.data_ptr()
-    call.probs = probs.data_ptr() if probs is not None else None
-    call.mask = mask.data_ptr() if mask is not None else None
-    call.conf = conf.data_ptr() if conf is not None else None
-    for m, t in enumerate(mout):
-        call.map_out[m] = t.data_ptr()
-    call.stream = _lib.current_stream(dev)
-    with _lib.device_guard(dev):
-        _lib.check(_lib.lib().uaps_tile_fold(C.byref(call)), "uaps_tile_fold")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.call("uaps_tile_fold", _lib.TileFoldCall, dev, B=B, C=Cc, H=H, W=W, th=th, tw=tw, oy=oy, ox=ox, n_chunks=n_chunks,
+              tiles_per_chunk=tpc, n_maps=len(ms), logits=[ptr(z) for z in zs or ()], maps=[[ptr(c) for c in cs] for cs in ms],
+              wy=ptr(wy), wx=ptr(wx), probs=ptr(probs), mask=ptr(mask), conf=ptr(conf), map_out=[ptr(t) for t in mout])
     return TiledResult(probs, mask, conf, tuple(mout))
 
 

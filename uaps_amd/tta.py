@@ -16,7 +16,6 @@ error.  One-channel sigmoid heads, vertical flips / rot90 views, per-view weight
 out of scope."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import NamedTuple, Optional, Sequence, Tuple
 
@@ -68,10 +67,8 @@ def tta_views(x: torch.Tensor, size: Tuple[int, int], flip: bool = True) -> torc
     x = x.detach().contiguous()
     B, Cin, H, W = x.shape
     out = torch.empty(((2 if flip else 1) * B, Cin, h, w), dtype=torch.float32, device=x.device)
-    call = _lib.TTAViewsCall(C.sizeof(_lib.TTAViewsCall), B, Cin, H, W, h, w, 1 if flip else 0, x.data_ptr(), out.data_ptr(),
-                             _lib.current_stream(x.device))
-    with _lib.device_guard(x.device):
-        _lib.check(_lib.lib().uaps_tta_views(C.byref(call)), "uaps_tta_views")
+    _lib.call("uaps_tta_views", _lib.TTAViewsCall, x.device, B=B, Cin=Cin, H=H, W=W, h=h, w=w, flip=1 if flip else 0, x=x.data_ptr(),
+              out=out.data_ptr())
     return out
 
 
@@ -121,17 +118,9 @@ def tta_fold(logits_list, out_size: Tuple[int, int], flip: bool = True, want: Se
     probs = torch.empty((B, Cc, H, W), dtype=torch.float32, device=dev) if "probs" in want else None
     mask = torch.empty((B, H, W), dtype=torch.int64, device=dev) if "mask" in want else None
     conf = torch.empty((B, H, W), dtype=torch.float32, device=dev) if "conf" in want else None
-    call = _lib.TTAFoldCall()
-    call.struct_size = C.sizeof(_lib.TTAFoldCall)
-    call.S, call.B, call.C, call.H, call.W, call.flip = S, B, Cc, H, W, 1 if flip else 0
-    for s, z in enumerate(zs):
-        call.logits[s], call.h[s], call.w[s] = z.data_ptr(), z.shape[2], z.shape[3]
-    call.probs_sum = probs.data_ptr() if probs is not None else None
-    call.mask = mask.data_ptr() if mask is not None else None
-    call.conf = conf.data_ptr() if conf is not None else None
-    call.stream = _lib.current_stream(dev)
-    with _lib.device_guard(dev):
-        _lib.check(_lib.lib().uaps_tta_fold(C.byref(call)), "uaps_tta_fold")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.call("uaps_tta_fold", _lib.TTAFoldCall, dev, S=S, B=B, C=Cc, H=H, W=W, flip=1 if flip else 0, logits=[ptr(z) for z in zs],
+              h=[z.shape[2] for z in zs], w=[z.shape[3] for z in zs], probs_sum=ptr(probs), mask=ptr(mask), conf=ptr(conf))
     return TTAResult(probs, mask, conf)
 
 

@@ -1475,6 +1475,100 @@ typedef struct uaps_shape_call {
 int uaps_shape_descriptors(const uaps_shape_call* call);
 
 /* ---------------------------------------------------------------------------------------------
+ * Defect skeletons: csrc/skeleton.hip.
+ *
+ * uaps_skeletonize: Guo and Hall's two-subiteration parallel thinning (CACM 32(3), 1989, algorithm A1) of a label map.  mask and
+ *   out int64 [B, H, W], out != mask.  Every selected class c (classes[0 .. n_classes), any order) is thinned on its own plane
+ *   P_c = (mask == c), 8-connected, everything outside the image background; a selected pixel that thinning removes becomes
+ *   `background`, every other value passes through untouched and is never claimed.
+ *   With the neighbours P2..P9 = N, NE, E, SE, S, SW, W, NW of a pixel,
+ *     C  = [!P2 & (P3 | P4)] + [!P4 & (P5 | P6)] + [!P6 & (P7 | P8)] + [!P8 & (P9 | P2)],
+ *     N1 = (P9 | P2) + (P3 | P4) + (P5 | P6) + (P7 | P8),  N2 = (P2 | P3) + (P4 | P5) + (P6 | P7) + (P8 | P9),  N = min(N1, N2),
+ *   a foreground pixel is deleted in a sub-iteration iff C == 1, 2 <= N <= 3 and (P2 | P3 | !P5) & P4 == 0 in the first
+ *   sub-iteration of an iteration, (P6 | P7 | !P9) & P8 == 0 in the second.  Every sub-iteration is a pure function of the
+ *   previous plane; an iteration is the two sub-iterations in that order.
+ *   out is the map after exactly min(max_iters, iterations to the fixed point) iterations.  converged uint8 [B]: 1 exactly where
+ *   the returned image is a fixed point for every selected class (one more iteration would delete nothing), else 0.
+ *   Launches: one pass packs the class planes into 64-bit words (a wave64 ballot of mask == c is the word), ceil(2 * max_iters / S)
+ *   thinning launches of S sub-iterations each (the last one the rest) on the packed planes, ping-pong between the two halves of
+ *   the workspace, one pass that tests the fixed point and one that writes the int64 map: fixed by the arguments.  A thinning
+ *   workgroup stages a band of rows x at most 512 columns of one plane in LDS with S halo rows and one halo word left and right;
+ *   the rule is evaluated bit-sliced on the words, without a table.  A per-image word records the last launch that removed
+ *   anything; a launch that finds the launch before it removed nothing from its image returns at once (both halves of the
+ *   workspace then hold the same planes).  Integers only, no atomics: the same bits from run to run, for every band height and S.
+ *   sub_iters 0: the S the library chooses; else an even value in [2, 64].  band_rows 0: the band height uaps_skeleton_band_rows
+ *   reports; > 0: that height.
+ *   workspace: uaps_skeleton_workspace_bytes(B, H, W, n_classes) bytes, 256-byte aligned, the call's alone until it has run; it
+ *   need not be zeroed.
+ * uaps_skeleton_band_rows (host only): the band height 0 resolves to for n_planes = n_classes + 1 and S sub-iterations a launch
+ *   (S 0: the chosen one).
+ * Errors (nothing launched): UAPS_EINVAL null struct, mask, out, converged or workspace, out == mask, non-positive dimension,
+ *   n_classes outside [1, 8], a duplicate class or one equal to `background`, max_iters outside [1, 2048], sub_iters odd or outside
+ *   {0} + [2, 64], negative band_rows, struct_size below this version's (the queries: a NULL result pointer, non-positive
+ *   dimension, n_classes outside [1, 8], n_planes outside [2, 9], S likewise); UAPS_ERANGE H or W above 4096, B * H * W * 8 >=
+ *   2 GiB, a workspace of 2 GiB or more (by dimensions), a forced band_rows whose planes do not fit 64 KiB of LDS;
+ *   UAPS_EWORKSPACE a workspace smaller than that or not 256-byte aligned.
+ *
+ * uaps_skeleton_stats: per defect of uaps_label_instances' `labels`, the counts that give a skeleton's length, its ends and its
+ *   branch points.  labels int32 [B, H, W], skel int64 [B, H, W] (the `out` of uaps_skeletonize on the mask the labels were formed
+ *   from).  A pixel p is a skeleton pixel of defect k iff labels[p] == k, 1 <= k <= max_instances, and skel[p] is one of
+ *   classes[0 .. n_classes).  Two skeleton pixels are linked iff they are 8-adjacent and belong to the same defect.
+ *     table int64 [B, max_instances, 7], row k - 1:
+ *       0 n_skel    skeleton pixels of the defect
+ *       1 n_orth    links between edge-adjacent skeleton pixels, each counted once
+ *       2 n_diag    links between diagonally adjacent skeleton pixels where neither of the two pixels edge-adjacent to both is a
+ *                   skeleton pixel of the same defect, each counted once
+ *       3 n_end     skeleton pixels with exactly one linked neighbour
+ *       4 n_branch  skeleton pixels whose cyclic sequence N, NE, E, SE, S, SW, W, NW of "is linked" has at least three 0 -> 1 steps
+ *       5 d2max, 6 d2sum   the maximum and the sum of max(plane, 0) over the skeleton pixels; plane int32 [B, H, W], or NULL: 0
+ *     A label <= 0 or above max_instances has no row and counts as "not the same defect".  Rows without a component are zero: the
+ *     call zeroes the whole table itself.
+ *   One zeroing launch and one pass: a wave owns 64 consecutive pixels of a row, reads rows y - 1, y, y + 1 and takes the side
+ *   neighbours from shuffles; a link is counted by its raster-first end (E, SW, S, SE); values are reduced over runs of equal
+ *   labels and flushed as uaps_shape_descriptors does (LDS copy of the table up to UAPS_SHAPE_LDS_ROWS rows, directly above it).
+ *   Integer atomics on non-negative values only.  No workspace; the call does not synchronise.
+ * Errors (nothing launched): UAPS_EINVAL null struct, labels, skel or table, non-positive dimension, max_instances < 1, n_classes
+ *   outside [1, 8], struct_size below this version's; UAPS_ERANGE as uaps_shape_descriptors (the table has 7 columns).
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_SKEL_MAX_CLASSES 8
+#define UAPS_SKEL_MAX_ITERS 2048
+#define UAPS_SKEL_MAX_SUB_ITERS 64
+#define UAPS_SKEL_MAX_EXTENT 4096
+#define UAPS_SKEL_COLUMNS 7
+typedef struct uaps_skeleton_call {
+    size_t struct_size;
+    int32_t B, H, W;
+    int32_t n_classes;
+    int32_t classes[UAPS_SKEL_MAX_CLASSES];
+    int32_t background;
+    int32_t max_iters;
+    int32_t sub_iters;                           /* 0: chosen by the library; else even, 2..64 (tests) */
+    int32_t band_rows;                           /* 0: chosen by the library; > 0: forced (tests) */
+    const int64_t* mask;                         /* [B][H][W] */
+    int64_t* out;                                /* [B][H][W] */
+    uint8_t* converged;                          /* [B] */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_skeleton_call;
+int uaps_skeleton_workspace_bytes(int B, int H, int W, int n_classes, size_t* bytes);
+int uaps_skeleton_band_rows(int H, int W, int n_planes, int S, int* rows);
+int uaps_skeletonize(const uaps_skeleton_call* call);
+
+typedef struct uaps_skeleton_stats_call {
+    uint32_t struct_size;
+    int32_t B, H, W, max_instances;
+    int32_t n_classes;
+    int32_t classes[UAPS_SKEL_MAX_CLASSES];
+    const int32_t* labels;                       /* [B][H][W] */
+    const int64_t* skel;                         /* [B][H][W] */
+    const int32_t* plane;                        /* [B][H][W] or NULL */
+    int64_t* table;                              /* [B][max_instances][7], written whole */
+    uaps_stream_t stream;
+} uaps_skeleton_stats_call;
+int uaps_skeleton_stats(const uaps_skeleton_stats_call* call);
+
+/* ---------------------------------------------------------------------------------------------
  * Tiled (sliding-window) full-resolution inference: csrc/tiled.hip.  An image of any size is cut into overlapping tiles of the size
  * the network runs at, the network runs on the tiles, and the tiles' probability maps are blended under a separable window.
  *

@@ -49,6 +49,11 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
                                                     counts and the statistics of a plane per defect in one pass; ShapeResult.props():
                                                     centroid, axes, orientation, perimeter, compactness, holes, inradius;
                                                     inference.predict_instances(..., shapes=True or "thickness")
+  skeletonize, skeleton_descriptors, SkeletonResult, SkeletonStats, SKELETON_COLUMNS
+                                                    defect skeletons: Guo-Hall thinning of the selected classes of a label map on
+                                                    packed bit planes, and per defect the skeleton's links, ends and branch points;
+                                                    SkeletonStats.props(): length, mean / max / rms width, end and branch counts;
+                                                    inference.predict_instances(..., skeleton=True or {"max_iters": n})
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -86,6 +91,8 @@ from .morphology import morphology          # (the function takes the submodule'
 from .components import components          # (likewise: uaps_amd.components(mask, steps, C))
 from .shapes import shape_descriptors, ShapeResult, SHAPE_COLUMNS
 from . import shapes
+from .skeleton import skeletonize, skeleton_descriptors, SkeletonResult, SkeletonStats, SKELETON_COLUMNS
+from . import skeleton
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

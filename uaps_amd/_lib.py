@@ -177,6 +177,10 @@ SIGNATURES = {
     "uaps_components_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
     "uaps_components": (C.c_int, [_PTR]),
     "uaps_shape_descriptors": (C.c_int, [_PTR]),
+    "uaps_skeleton_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
+    "uaps_skeleton_band_rows": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)]),
+    "uaps_skeletonize": (C.c_int, [_PTR]),
+    "uaps_skeleton_stats": (C.c_int, [_PTR]),
     "uaps_tile_origins": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
     "uaps_tile_cut": (C.c_int, [_PTR]),
     "uaps_tile_fold": (C.c_int, [_PTR]),
@@ -398,6 +402,24 @@ class ShapeCall(C.Structure):
     """uaps_shape_call (include/uaps_hip.h): every operand of uaps_shape_descriptors, size-versioned."""
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("max_instances", C.c_int32),
                 ("labels", C.c_void_p), ("plane", C.c_void_p), ("table", C.c_void_p), ("stream", C.c_void_p)]
+
+
+SKEL_MAX_CLASSES, SKEL_MAX_ITERS, SKEL_MAX_SUB_ITERS, SKEL_MAX_EXTENT, SKEL_COLUMNS = 8, 2048, 64, 4096, 7       # UAPS_SKEL_*
+
+
+class SkeletonCall(C.Structure):
+    """uaps_skeleton_call (include/uaps_hip.h): every operand of uaps_skeletonize, size-versioned."""
+    _fields_ = [("struct_size", C.c_size_t), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("n_classes", C.c_int32),
+                ("classes", C.c_int32 * SKEL_MAX_CLASSES), ("background", C.c_int32), ("max_iters", C.c_int32),
+                ("sub_iters", C.c_int32), ("band_rows", C.c_int32), ("mask", C.c_void_p), ("out", C.c_void_p),
+                ("converged", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class SkeletonStatsCall(C.Structure):
+    """uaps_skeleton_stats_call (include/uaps_hip.h): every operand of uaps_skeleton_stats, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("max_instances", C.c_int32),
+                ("n_classes", C.c_int32), ("classes", C.c_int32 * SKEL_MAX_CLASSES), ("labels", C.c_void_p), ("skel", C.c_void_p),
+                ("plane", C.c_void_p), ("table", C.c_void_p), ("stream", C.c_void_p)]
 
 
 TILE_MAX_CHUNKS, TILE_MAX_MAPS = 32, 2  # UAPS_TILE_MAX_CHUNKS, UAPS_TILE_MAX_MAPS

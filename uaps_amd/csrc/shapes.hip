@@ -24,16 +24,20 @@
 #include <stdint.h>
 #include <string.h>
 #include "cc_common.hpp"
+#include "table_flush.hpp"
 
 namespace {
 using namespace uaps::loss;
 using uaps::cc::run_end;
+using uaps::table::table_lds_zero;
+using uaps::table::table_lds_flush;
 
 constexpr int kCols = UAPS_SHAPE_COLUMNS;
 constexpr int kSpanLds = 4, kSpanDirect = uaps::cc::kSpan;      // groups of 64 pixels an item, per flush form
 constexpr int kItems = 2;                               // items a wave
-constexpr int kLdsRows = UAPS_SHAPE_LDS_ROWS;
-constexpr int kMaxGrid = 1 << 24;
+constexpr int kLdsRows = uaps::table::kLdsRows;
+constexpr int kMaxGrid = uaps::table::kMaxGrid;
+constexpr int kMaxCol = 9;                              // pmax: the table's one maximum column (table_flush.hpp)
 typedef unsigned long long u64;
 
 struct ShapeArgs {
@@ -44,12 +48,10 @@ struct ShapeArgs {
     u64* table;
 };
 
-__global__ __launch_bounds__(kThreads) void shape_zero_kernel(u64* table, long n) {
-    for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) table[i] = 0ull;
-}
-
 // the sum of the squares of 0 .. m (m >= -1)
 __device__ __forceinline__ long long squares_to(long long m) { return m * (m + 1) * (2 * m + 1) / 6; }
+
+__global__ __launch_bounds__(kThreads) void shape_zero_kernel(u64* table, long n) { uaps::table::table_zero(table, n); }
 
 struct RunAcc { int x0, n; u64 q, ps; unsigned pm; };
 
@@ -66,7 +68,7 @@ __device__ __forceinline__ void shape_send(u64* rows, int k, int y, const RunAcc
     for (int c = 0; c < 9; ++c)
         if (v[c]) atomicAdd(row + c, v[c]);
     if (PLANE) {
-        if (r.pm) atomicMax(row + 9, (u64)r.pm);
+        if (r.pm) atomicMax(row + kMaxCol, (u64)r.pm);
         if (r.ps) atomicAdd(row + 10, r.ps);
     }
 }
@@ -80,10 +82,7 @@ __global__ __launch_bounds__(kThreads) void shape_accumulate_kernel(ShapeArgs a)
     const int words = a.M * kCols;
     u64* const out = a.table + (long)b * words;
     u64* const rows = LDS ? acc : out;
-    if (LDS) {
-        for (int i = threadIdx.x; i < words; i += kThreads) acc[i] = 0ull;
-        __syncthreads();
-    }
+    if (LDS) table_lds_zero(acc, words);
     const long HW = (long)a.H * a.W;
     const int* lab = a.labels + (long)b * HW;
     const int* pl = PLANE ? a.plane + (long)b * HW : nullptr;
@@ -168,15 +167,7 @@ __global__ __launch_bounds__(kThreads) void shape_accumulate_kernel(ShapeArgs a)
         }
         if (pend_k > 0 && lane == 0) shape_send<PLANE>(rows, pend_k, y, pend);
     }
-    if (LDS) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < words; i += kThreads) {
-            const u64 v = acc[i];
-            if (v == 0ull) continue;
-            if (i % kCols == 9) atomicMax(out + i, v);
-            else atomicAdd(out + i, v);
-        }
-    }
+    if (LDS) table_lds_flush<kCols, kMaxCol>(acc, out, words);
 }
 
 constexpr size_t kShapeV1 = offsetof(uaps_shape_call, stream) + sizeof(uaps_stream_t);

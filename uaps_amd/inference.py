@@ -247,7 +247,7 @@ def _with_shapes(inst, shapes, connectivity: int):
 
 @torch.no_grad()
 def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, tiled=None, min_area: int = 1, connectivity: int = 8,
-                      max_instances: int = 256, cleanup=None, components=None, shapes=False):
+                      max_instances: int = 256, cleanup=None, components=None, shapes=False, skeleton=False):
     """Defects instead of pixels: instances.label_instances on the main head's arg-max mask, with maps = (confidence, uncertainty).
     The confidence is the main head's largest softmax; with tta (True, or a tuple of scales) mask and confidence are those of
     tta.predict_tta.  The uncertainty is consistency.uncertainty_map(main, aux1) of the plain forward where the model has an auxiliary
@@ -258,10 +258,16 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     instances.InstanceResult (records() lists the defects).
     shapes=True, or "thickness": a shapes.ShapeResult instead -- shapes.shape_descriptors of that InstanceResult (with thickness=True
     for "thickness"), which `.instances` holds; its props() and records() add centroid, axes, orientation, perimeter, holes and the
-    like to every defect.  Under all three paths, after the clean-up chains."""
+    like to every defect.  Under all three paths, after the clean-up chains.
+    skeleton=True, or a dict {"max_iters": n}: a skeleton.SkeletonStats instead -- skeleton.skeletonize of the mask that is labelled
+    (after the clean-up chains, every class but 0), then skeleton.skeleton_descriptors of the InstanceResult; its props() and
+    records() add length, widths, end and branch counts to every defect.  With shapes also set the ShapeResult is its `.shapes`
+    and records() merges both.  Under all three paths."""
     from . import instances
     if shapes not in (False, True, "thickness"):
         raise ValueError("predict_instances: shapes is False, True or \"thickness\"")
+    if not (skeleton is False or skeleton is True or (isinstance(skeleton, dict) and set(skeleton) <= {"max_iters"})):
+        raise ValueError("predict_instances: skeleton is False, True or a dict {\"max_iters\": n}")
     clean = cleanup is not None or components is not None
     if components is not None:
         from .components import check_steps as check_component_steps
@@ -269,7 +275,7 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     tiled_kw, want = None, ("mask", "conf", "heads")
     if tiled:
         # (the class count of the clean-up is the blended maps' channel count: they are asked for beside the mask then)
-        tiled_kw, want = _tiled_kwargs(tiled, tta, "predict_instances"), ("mask", "conf") + (("probs",) if clean else ())
+        tiled_kw, want = _tiled_kwargs(tiled, tta, "predict_instances"), ("mask", "conf") + (("probs",) if clean or skeleton is not False else ())
         tiled_kw.setdefault("uncertainty", "auto")
     f = _forward(model, images, tta, tiled_kw, want)
     maps = (f.conf,) + f.maps
@@ -278,8 +284,14 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     mask = f.mask
     if clean:
         mask = _cleaned(mask, cleanup, (f.scored if f.heads is None else f.heads[0]).shape[1], components)
-    return _with_shapes(instances.label_instances(mask, maps, connectivity=connectivity, min_area=min_area, max_instances=max_instances),
-                        shapes, connectivity)
+    inst = instances.label_instances(mask, maps, connectivity=connectivity, min_area=min_area, max_instances=max_instances)
+    if skeleton is False:
+        return _with_shapes(inst, shapes, connectivity)
+    from .skeleton import skeletonize, skeleton_descriptors
+    num_classes = (f.scored if f.heads is None else f.heads[0]).shape[1]
+    skel = skeletonize(mask, num_classes, **(skeleton if isinstance(skeleton, dict) else {}))
+    stats = skeleton_descriptors(inst, skel)
+    return stats._replace(shapes=_with_shapes(inst, shapes, connectivity)) if shapes else stats
 
 
 def load_for_inference(model: torch.nn.Module, checkpoint_path: str, device: Optional[torch.device] = None) -> Dict:

@@ -1855,6 +1855,55 @@ typedef struct uaps_plane_curves_call {
 } uaps_plane_curves_call;
 int uaps_plane_curves(const uaps_plane_curves_call* call);
 
+/* ---------------------------------------------------------------------------------------------
+ * Defect convex hulls: csrc/hull.hip.
+ *
+ * uaps_hull_descriptors: the convex hull of every component of the `labels` of uaps_label_instances and what its strict vertices
+ *   give: the area, the farthest pair (maximum Feret diameter), the minimum caliper width and the minimum-area rectangle.
+ *   labels int32 [B, H, W]: 0 = no component, k >= 1 = component k of that image.
+ *   Geometry.  A pixel (y, x) is the closed unit square [x, x + 1] x [y, y + 1]; the hull of component k is the convex hull of the
+ *   squares of ALL pixels labelled k, connected or not, so its vertices lie on the corner lattice 0..W x 0..H.  Only strict
+ *   vertices count.  Order: v_0 is the smallest vertex (y, then x), v_1 the other end of the horizontal top edge, and so on
+ *   (clockwise on the screen).  Edge i runs from v_i to v_{i+1} (cyclic) with the vector e = (ex, ey); for a point p
+ *     c(p) = ex (py - vy) - ey (px - vx)  (>= 0 on the hull),   d(p) = ex (px - vx) + ey (py - vy).
+ *     table int64 [B, max_instances, 17]   row k - 1 of image b, 1 <= k <= max_instances:
+ *       0      nv        the number of strict vertices (>= 4)
+ *       1      area2     twice the hull's area: the shoelace sum
+ *       2..6   fmax_sq, f_y0, f_x0, f_y1, f_x1   the largest squared distance between two vertices and the pair that attains
+ *                        it, (y0, x0) < (y1, x1) lexicographically; among tied pairs the smallest (y0, x0, y1, x1)
+ *       7..9   w_ey, w_ex, w_c   the edge that minimises C^2 / |e|^2, C the largest c(p) over the vertices: its vector and C.
+ *                        The minimum caliper width is w_c / |e|
+ *       10..16 r_y, r_x, r_ey, r_ex, r_dmin, r_dmax, r_c   the edge that minimises (dmax - dmin) C / |e|^2, dmin and dmax the
+ *                        extremes of d(p) over the vertices: its start vertex, its vector, dmin <= 0, dmax and C.  The
+ *                        minimum-area rectangle is flush with that edge; its sides are (dmax - dmin) / |e| and C / |e|
+ *     Both minimisations compare the fractions exactly (cross-multiplied in 128-bit integers); ties go to the edge with the
+ *     lowest index.  A label <= 0 or above max_instances has no row.  Rows without a pixel are zero; every row is written once,
+ *     whatever table and workspace held before.  All columns are exact integers; no float is used.
+ *   Three launches: the workspace is zeroed; one pass over the labels raises, per run of equal labels along a row, the column
+ *   extents of that (image, component, row) and the row range of the component with integer atomicMax (the minima are stored
+ *   inverted); one workgroup per (image, component) builds the two chains of lattice-line extremes in LDS (8 (H + 1) bytes),
+ *   reduces them to the strict vertices and evaluates the columns.  The same bits from run to run.  The call does not synchronise.
+ *   workspace: uaps_hull_workspace_bytes(B, H, W, max_instances) = B * max_instances * (H + 1) * 8 bytes (rounded up to 256),
+ *   256-byte aligned, the call's alone until it has run; it need not be zeroed.
+ * Errors (nothing launched): UAPS_EINVAL null struct, labels, table or workspace (the query: a NULL result pointer), table ==
+ *   labels, non-positive dimension, max_instances < 1, struct_size below this version's; UAPS_ERANGE H or W above
+ *   UAPS_HULL_MAX_EXTENT, B * H * W * 8 >= 2 GiB, a table or a workspace of 2 GiB or more (by dimensions); UAPS_EWORKSPACE a
+ *   workspace smaller than that or not 256-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_HULL_COLUMNS 17
+#define UAPS_HULL_MAX_EXTENT 4096
+typedef struct uaps_hull_call {
+    uint32_t struct_size;
+    int32_t B, H, W, max_instances;
+    const int32_t* labels;                       /* [B][H][W] */
+    int64_t* table;                              /* [B][max_instances][17], written whole */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_hull_call;
+int uaps_hull_workspace_bytes(int B, int H, int W, int max_instances, size_t* bytes);
+int uaps_hull_descriptors(const uaps_hull_call* call);
+
 #ifdef __cplusplus
 }
 #endif

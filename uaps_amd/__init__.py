@@ -54,6 +54,10 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
                                                     packed bit planes, and per defect the skeleton's links, ends and branch points;
                                                     SkeletonStats.props(): length, mean / max / rms width, end and branch counts;
                                                     inference.predict_instances(..., skeleton=True or {"max_iters": n})
+  hull_descriptors, HullResult, HULL_COLUMNS        defect convex hulls from the labels of label_instances: strict vertices, area,
+                                                    farthest pair, minimum caliper width and minimum-area rectangle as exact
+                                                    integers; HullResult.props(): solidity, Feret diameters, the rotated box;
+                                                    inference.predict_instances(..., hull=True)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -93,6 +97,8 @@ from .shapes import shape_descriptors, ShapeResult, SHAPE_COLUMNS
 from . import shapes
 from .skeleton import skeletonize, skeleton_descriptors, SkeletonResult, SkeletonStats, SKELETON_COLUMNS
 from . import skeleton
+from .hull import hull_descriptors, HullResult, HULL_COLUMNS
+from . import hull
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -193,6 +193,8 @@ SIGNATURES = {
     "uaps_curves_workspace_bytes": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_size_t)]),
     "uaps_score_curves": (C.c_int, [_PTR]),
     "uaps_plane_curves": (C.c_int, [_PTR]),
+    "uaps_hull_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
+    "uaps_hull_descriptors": (C.c_int, [_PTR]),
 }
 
 
@@ -420,6 +422,16 @@ class SkeletonStatsCall(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("max_instances", C.c_int32),
                 ("n_classes", C.c_int32), ("classes", C.c_int32 * SKEL_MAX_CLASSES), ("labels", C.c_void_p), ("skel", C.c_void_p),
                 ("plane", C.c_void_p), ("table", C.c_void_p), ("stream", C.c_void_p)]
+
+
+HULL_COLUMNS, HULL_MAX_EXTENT = 17, 4096       # UAPS_HULL_COLUMNS, UAPS_HULL_MAX_EXTENT
+
+
+class HullCall(C.Structure):
+    """uaps_hull_call (include/uaps_hip.h): every operand of uaps_hull_descriptors, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("max_instances", C.c_int32),
+                ("labels", C.c_void_p), ("table", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
 
 
 TILE_MAX_CHUNKS, TILE_MAX_MAPS = 32, 2  # UAPS_TILE_MAX_CHUNKS, UAPS_TILE_MAX_MAPS

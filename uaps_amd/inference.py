@@ -247,7 +247,7 @@ def _with_shapes(inst, shapes, connectivity: int):
 
 @torch.no_grad()
 def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, tiled=None, min_area: int = 1, connectivity: int = 8,
-                      max_instances: int = 256, cleanup=None, components=None, shapes=False, skeleton=False):
+                      max_instances: int = 256, cleanup=None, components=None, shapes=False, skeleton=False, hull=False):
     """Defects instead of pixels: instances.label_instances on the main head's arg-max mask, with maps = (confidence, uncertainty).
     The confidence is the main head's largest softmax; with tta (True, or a tuple of scales) mask and confidence are those of
     tta.predict_tta.  The uncertainty is consistency.uncertainty_map(main, aux1) of the plain forward where the model has an auxiliary
@@ -262,8 +262,13 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     skeleton=True, or a dict {"max_iters": n}: a skeleton.SkeletonStats instead -- skeleton.skeletonize of the mask that is labelled
     (after the clean-up chains, every class but 0), then skeleton.skeleton_descriptors of the InstanceResult; its props() and
     records() add length, widths, end and branch counts to every defect.  With shapes also set the ShapeResult is its `.shapes`
-    and records() merges both.  Under all three paths."""
+    and records() merges both.  Under all three paths.
+    hull=True: a hull.HullResult instead -- hull.hull_descriptors of that InstanceResult; its `.also` holds what the same call returns
+    without hull= (the ShapeResult, the SkeletonStats, or None for the bare InstanceResult), and its props() and records() add
+    solidity, the Feret diameters and the minimum-area rectangle to every defect.  Under all three paths."""
     from . import instances
+    if hull is not False and hull is not True:
+        raise ValueError("predict_instances: hull is False or True")
     if shapes not in (False, True, "thickness"):
         raise ValueError("predict_instances: shapes is False, True or \"thickness\"")
     if not (skeleton is False or skeleton is True or (isinstance(skeleton, dict) and set(skeleton) <= {"max_iters"})):
@@ -286,12 +291,17 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
         mask = _cleaned(mask, cleanup, (f.scored if f.heads is None else f.heads[0]).shape[1], components)
     inst = instances.label_instances(mask, maps, connectivity=connectivity, min_area=min_area, max_instances=max_instances)
     if skeleton is False:
-        return _with_shapes(inst, shapes, connectivity)
-    from .skeleton import skeletonize, skeleton_descriptors
-    num_classes = (f.scored if f.heads is None else f.heads[0]).shape[1]
-    skel = skeletonize(mask, num_classes, **(skeleton if isinstance(skeleton, dict) else {}))
-    stats = skeleton_descriptors(inst, skel)
-    return stats._replace(shapes=_with_shapes(inst, shapes, connectivity)) if shapes else stats
+        res = _with_shapes(inst, shapes, connectivity)
+    else:
+        from .skeleton import skeletonize, skeleton_descriptors
+        num_classes = (f.scored if f.heads is None else f.heads[0]).shape[1]
+        skel = skeletonize(mask, num_classes, **(skeleton if isinstance(skeleton, dict) else {}))
+        stats = skeleton_descriptors(inst, skel)
+        res = stats._replace(shapes=_with_shapes(inst, shapes, connectivity)) if shapes else stats
+    if not hull:
+        return res
+    from .hull import hull_descriptors
+    return hull_descriptors(inst)._replace(also=None if res is inst else res)
 
 
 def load_for_inference(model: torch.nn.Module, checkpoint_path: str, device: Optional[torch.device] = None) -> Dict:

@@ -1194,6 +1194,32 @@ int uaps_bn_act_bwd_grouped_bias_h(const uaps_call_hints* hints, const float* do
                                    float* dconv_bias, void* workspace, size_t workspace_bytes, uaps_stream_t stream);
 int uaps_bn_act_bwd_apply_h(const uaps_call_hints* hints, const float* dout, const float* y, const float* coef, float slope, int B, int C,
                             int H, int W, int groups, float* dy, uaps_stream_t stream);
+/* Encoder glue.  Three forms that spare the encoder's serial phases a launch and a tensor read each; every result is the
+ * bits the separate launches produce.  Outside its form each returns UAPS_ENOFORM with nothing launched and nothing written.
+ * uaps_bn_act_fwd_train_partials_pool_h: uaps_bn_act_fwd_train_partials_h (no dropout, no residual) whose apply pass also writes
+ *   MaxPool2d(2) of the activated tensor -- pooled [B,C,H/2,W/2] and idx uint8 of that shape, exactly what uaps_maxpool2x2_fwd would
+ *   make of `out`.  Form: uaps_bn_apply_pool_support(H, W) == UAPS_OK (H even, W % 8 == 0, 4096 % (2 W) == 0), 16-byte aligned
+ *   y / out / pooled, 4-byte aligned idx.
+ * uaps_fanin_perturbed_bn_sums_h: uaps_fanin_perturbed for a feature map that a train-mode BatchNorm + LeakyReLU (no dropout)
+ *   produced from the raw conv output y; the same pass also forms that BatchNorm's backward sums over (out, y): partials float2
+ *   [C][B][ceil(H W / 4096)].  Form: what uaps_fanin_perturbed takes, 16-byte aligned y, 8-byte aligned partials, B C <= 65535.
+ * uaps_bn_act_bwd_partials_h: the dx pass of uaps_bn_act_bwd_grouped_bias_h alone, from such partials (dconv_bias may be NULL). */
+int uaps_bn_apply_pool_support(int H, int W);
+int uaps_bn_act_fwd_train_partials_pool_h(const uaps_call_hints* hints, const void* partials, int parts_per_image, const float* y,
+                                          const float* conv_bias, const float* gamma, const float* beta, float* running_mean,
+                                          float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float slope,
+                                          float drop_p, uint64_t seed, uint64_t offset, int B, int C, int H, int W, int groups, float* out,
+                                          float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes,
+                                          uaps_stream_t stream, float* pooled, uint8_t* idx);
+int uaps_fanin_perturbed_bn_sums_h(const uaps_call_hints* hints, const float* const* g_host, const int* mode_host,
+                                   const uint8_t* const* keep_host, const uint64_t* offsets_host, int n, int groups, uint64_t seed,
+                                   float range, float p, int B, int C, int H, int W, float* out, const float* y, const float* gamma,
+                                   const float* beta, const float* save_mean, const float* save_invstd, float slope, void* partials,
+                                   uaps_stream_t stream);
+int uaps_bn_act_bwd_partials_h(const uaps_call_hints* hints, const void* partials, int parts_per_image, const float* dout, const float* y,
+                               const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float slope, int B,
+                               int C, int H, int W, int groups, float* dy, float* dgamma, float* dbeta, float* dconv_bias,
+                               uaps_stream_t stream);
 int uaps_up_cat_fwd_h(const uaps_call_hints* hints, const float* skip, const float* low, float* out, int B, int Cs, int Cl, int h, int w,
                       uaps_stream_t stream);
 int uaps_cat2_h(const uaps_call_hints* hints, const float* a, const float* b, float* out, long n, uaps_stream_t stream);

@@ -207,6 +207,11 @@ HINTED = ("uaps_conv_fwd", "uaps_conv_fwd_stats", "uaps_conv_fwd_bn", "uaps_conv
 for _n in HINTED:
     SIGNATURES[_n + "_h"] = (SIGNATURES[_n][0], [_PTR] + list(SIGNATURES[_n][1]))
 del _n
+# the encoder-glue forms (include/uaps_hip.h): hinted entry points without an unhinted twin
+SIGNATURES["uaps_bn_apply_pool_support"] = (C.c_int, [C.c_int, C.c_int])
+SIGNATURES["uaps_bn_act_fwd_train_partials_pool_h"] = (C.c_int, list(SIGNATURES["uaps_bn_act_fwd_train_partials_h"][1]) + [_PTR, _PTR])
+SIGNATURES["uaps_fanin_perturbed_bn_sums_h"] = (C.c_int, [_PTR] + list(SIGNATURES["uaps_fanin_perturbed"][1][:-1]) + [_PTR] * 5 + [C.c_float, _PTR, _PTR])
+SIGNATURES["uaps_bn_act_bwd_partials_h"] = (C.c_int, [_PTR, _PTR, C.c_int] + [_PTR] * 6 + [C.c_float] + [C.c_int] * 5 + [_PTR] * 5)
 
 
 class UapsHipError(RuntimeError):

@@ -30,6 +30,7 @@ DOC = {
     "UAPS_FUSED_UP_FOLD": "the input gradient of up4's first convolution folds its up-sampled half to the low resolution inside the row kernel (csrc/up_bwd_row.hip)",
     "UAPS_LAZY_BN_BWD": "BatchNorm backward in two halves on the 256-wide decoder layers (lazybn)",
     "UAPS_PAIR_CFG": "cfg bits of the pair-loss kernels (diagnosis)",
+    "UAPS_FUSED_ENC_GLUE": "encoder: the 2x2 max-pool written by the BatchNorm apply pass in front of it, the BatchNorm-backward sums formed by the feature fan-in",
     "UAPS_FUSED_FANOUT": "all perturbed copies of a feature map written by one pass over it",
     "UAPS_EPILOGUE_STATS": "BatchNorm statistics in the producing convolution's epilogue",
     "UAPS_VIRTUAL_CAT": "two-source convolutions instead of a materialised torch.cat in the UpBlocks",

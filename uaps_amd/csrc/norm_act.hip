@@ -16,12 +16,13 @@
 #include "../../include/uaps_hip.h"
 #include "philox.hpp"
 #include "hints.hpp"
+#include "bn_pieces.hpp"
 
 namespace {
-using uaps::philox4x32_10; using uaps::u01; using uaps::U4; using uaps::pick;
+using uaps::philox4x32_10; using uaps::u01; using uaps::U4; using uaps::pick; using uaps::block_sum2; using uaps::dpre;
 
-constexpr int kThreads = 256;
-constexpr int kChunk = 4096;       // floats per block: 4 float4 per thread
+constexpr int kThreads = uaps::kBnThreads;
+constexpr int kChunk = uaps::kBnChunk;       // floats per block: 4 float4 per thread
 
 inline int nchunks_for(long HW) { return (int)((HW + kChunk - 1) / kChunk); }
 inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
@@ -38,18 +39,6 @@ inline BnWs carve(void* ws, int B, int C, long HW) {
     w.coef = (float*)((char*)ws + align256((size_t)C * B * nchunks_for(HW) * sizeof(float2)));
     w.maxes = (float*)((char*)w.coef + align256((size_t)4 * C * kMaxGroups * sizeof(float)));
     return w;
-}
-
-__device__ __forceinline__ float2 block_sum2(float a, float b) {
-    __shared__ float2 red[kThreads / 64];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = make_float2(a, b);
-    __syncthreads();
-    float2 r = red[0];
-#pragma unroll
-    for (int w = 1; w < kThreads / 64; ++w) { r.x += red[w].x; r.y += red[w].y; }
-    return r;
 }
 
 // ---- forward pass 1: per-chunk (sum, sum of squares) ------------------------------------------------
@@ -224,13 +213,7 @@ __global__ __launch_bounds__(kThreads) void bn_apply_kernel(const float* __restr
 }
 
 // ---- backward helpers -------------------------------------------------------------------------------------
-// d(pre-activation) from d(out): dropout mask/scale, then LeakyReLU slope chosen by the sign of the
-// recomputed BN output z (torch: grad * (z > 0 ? 1 : slope)).
-__device__ __forceinline__ float dpre(float dout, float yv, float mu, float sc, float sh, float slope) {
-    const float z = (yv - mu) * sc + sh;
-    return z > 0.f ? dout : dout * slope;
-}
-
+// (dpre, d(pre-activation) from d(out), and block_sum2: bn_pieces.hpp)
 template <bool VEC, bool DROP>
 __global__ __launch_bounds__(kThreads) void bn_bwd_sums_kernel(const float* __restrict__ dout, const float* __restrict__ y, int C,
                                                                long HW, int nchunks, const float* __restrict__ mean,
@@ -534,7 +517,8 @@ static int bn_fwd_train_impl(const uaps_call_hints& hints, const float2* given_p
                                              float* running_mean, float* running_var, int64_t* num_batches_tracked,
                                              float momentum, float eps, float slope, float drop_p, uint64_t seed, uint64_t offset,
                                              int B, int C, int H, int W, int groups, float* out, float* save_mean,
-                                             float* save_invstd, void* ws, size_t ws_bytes, uaps_stream_t stream) {
+                                             float* save_invstd, void* ws, size_t ws_bytes, uaps_stream_t stream,
+                                             float* pooled = nullptr, uint8_t* pool_idx = nullptr) {
     // given partials: formed about the shift the caller names; own statistics pass: about running_mean - conv_bias
     const float* shm = given_partials ? hints.stats_mean : running_mean;
     const float* shb = given_partials ? hints.stats_bias : conv_bias;
@@ -544,8 +528,14 @@ static int bn_fwd_train_impl(const uaps_call_hints& hints, const float2* given_p
     if (groups < 1 || groups > kMaxGroups || B % groups) return UAPS_EINVAL;
     const float* res = hints.residual;
     if (res && (drop_p > 0.f || !al16(res))) return UAPS_EINVAL;      // the join has no dropout; the residual is a tensor like y
-    // y read and the activated tensor written (+ the residual read; + one more read of y when the statistics pass runs here)
-    uaps::account_bytes(4.0 * B * C * H * W * (2.0 + (given_partials ? 0.0 : 1.0) + (hints.residual ? 1.0 : 0.0)));
+    if (pooled) {      // the form that also writes the 2x2 max-pool (enc_glue.hip): refused before anything is launched or written
+        if (uaps_bn_apply_pool_support(H, W) != UAPS_OK || drop_p > 0.f || res || !pool_idx) return UAPS_ENOFORM;
+        if (!al16(y) || !al16(out) || !al16(pooled) || (reinterpret_cast<uintptr_t>(pool_idx) & 3)) return UAPS_ENOFORM;
+    }
+    // y read and the activated tensor written (+ the residual read; + one more read of y when the statistics pass runs here;
+    // + the pooled map and its index bytes)
+    uaps::account_bytes(4.0 * B * C * H * W * (2.0 + (given_partials ? 0.0 : 1.0) + (hints.residual ? 1.0 : 0.0)) +
+                        (pooled ? 1.25 * B * C * H * W : 0.0));
     const long HW = (long)H * W;
     if (ws_bytes < bn_ws_bytes(B, C, HW)) return UAPS_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -562,7 +552,9 @@ static int bn_fwd_train_impl(const uaps_call_hints& hints, const float2* given_p
                        running_var, num_batches_tracked, momentum, eps, save_mean, save_invstd, w.coef, C, (float2*)nullptr, shm, shb);
     const float dscale = 1.f / (1.f - drop_p);
 #define UAPS_APPLY(V, D) hipLaunchKernelGGL((bn_apply_kernel<V, D>), grid, dim3(kThreads), 0, s, y, out, C, HW, save_mean, w.coef, slope, drop_p, dscale, seed, offset, Bg, (const uint32_t*)uaps_get_step_state(), res, hints.out_amax)
-    if (vec) { if (drop_p > 0.f) UAPS_APPLY(true, true); else UAPS_APPLY(true, false); }
+    if (pooled)
+        uaps::launch_bn_apply_pool(y, out, pooled, pool_idx, B, C, H, W, save_mean, w.coef, slope, Bg, hints.out_amax, s);      // enc_glue.hip
+    else if (vec) { if (drop_p > 0.f) UAPS_APPLY(true, true); else UAPS_APPLY(true, false); }
     else { if (drop_p > 0.f) UAPS_APPLY(false, true); else UAPS_APPLY(false, false); }
 #undef UAPS_APPLY
     return (int)hipGetLastError();
@@ -597,6 +589,14 @@ extern "C" int uaps_bn_act_fwd_train_partials_h(const uaps_call_hints* hints, UA
     UAPS_READ_HINTS(hints, h);
     if (!partials || parts_per_image <= 0) return UAPS_EINVAL;
     return bn_fwd_train_impl(h, UAPS_BN_PARTIALS_ARGS);
+}
+// The same, the apply pass also writing MaxPool2d(2) of the activated tensor: pooled [B,C,H/2,W/2] and idx uint8 of that shape, value,
+// arg-max position, tie and NaN rule of uaps_maxpool2x2_fwd.  Outside uaps_bn_apply_pool_support(H, W), with dropout, a residual or
+// misaligned tensors: UAPS_ENOFORM, nothing launched, nothing written.
+extern "C" int uaps_bn_act_fwd_train_partials_pool_h(const uaps_call_hints* hints, UAPS_BN_PARTIALS_PARAMS, float* pooled, uint8_t* idx) {
+    UAPS_READ_HINTS(hints, h);
+    if (!partials || parts_per_image <= 0 || !pooled || !idx) return UAPS_EINVAL;
+    return bn_fwd_train_impl(h, UAPS_BN_PARTIALS_ARGS, pooled, idx);
 }
 #undef UAPS_BN_PARTIALS_PARAMS
 #undef UAPS_BN_PARTIALS_ARGS
@@ -662,23 +662,30 @@ extern "C" int uaps_bn_act_fwd_eval(const float* y, const float* conv_bias, cons
 static int bn_bwd_impl(float* amax_out, const float* dout, const float* y, const float* gamma, const float* beta,
                                        const float* save_mean, const float* save_invstd, float slope, float drop_p, uint64_t seed,
                                        uint64_t offset, int B, int C, int H, int W, int groups, float* dy, float* dgamma,
-                                       float* dbeta, float* dconv_bias, void* ws, size_t ws_bytes, uaps_stream_t stream) {
+                                       float* dbeta, float* dconv_bias, void* ws, size_t ws_bytes, uaps_stream_t stream,
+                                       const float2* given_partials = nullptr, int given_parts_per_image = 0) {
+    // given partials (float2 [C][B][parts_per_image], formed by the kernel that wrote dout: uaps_fanin_perturbed_bn_sums): the dx pass
+    // alone, no workspace; only without dropout (the BatchNorm behind a feature fan-out has none)
     int rc = check(dout, dy, B, C, H, W);
     if (rc) return rc;
-    if (!y || !gamma || !beta || !save_mean || !save_invstd || !dgamma || !dbeta || !ws || !(drop_p >= 0.f && drop_p < 1.f)) return UAPS_EINVAL;
+    if (!y || !gamma || !beta || !save_mean || !save_invstd || !dgamma || !dbeta || !(drop_p >= 0.f && drop_p < 1.f)) return UAPS_EINVAL;
+    if (given_partials ? (given_parts_per_image <= 0 || drop_p > 0.f) : !ws) return UAPS_EINVAL;
     if (groups < 1 || groups > kMaxGroups || B % groups) return UAPS_EINVAL;
     const long HW = (long)H * W;
-    if (ws_bytes < bn_ws_bytes(B, C, HW)) return UAPS_EWORKSPACE;
-    uaps::account_bytes(4.0 * B * C * HW * 5.0);      // the reductions need all of (d, y) before dx can start: 2 + 2 reads, 1 write
+    if (!given_partials && ws_bytes < bn_ws_bytes(B, C, HW)) return UAPS_EWORKSPACE;
+    uaps::account_bytes(4.0 * B * C * HW * (given_partials ? 3.0 : 5.0));      // the reductions need all of (d, y) before dx can start: 2 + 2 reads, 1 write
     hipStream_t s = (hipStream_t)stream;
-    const BnWs w = carve(ws, B, C, HW);
     const int nch = nchunks_for(HW), Bg = B / groups;
+    BnWs w{};
+    if (given_partials) w.partials = const_cast<float2*>(given_partials); else w = carve(ws, B, C, HW);
+    const int nch_p = given_partials ? given_parts_per_image : nch;
     const dim3 grid(nch, B * C);
     const bool vec = (HW % 4 == 0) && al16(y) && al16(dout) && al16(dy);
     const float dscale = 1.f / (1.f - drop_p);
 #define UAPS_SUMS(V, D) hipLaunchKernelGGL((bn_bwd_sums_kernel<V, D>), grid, dim3(kThreads), 0, s, dout, y, C, HW, nch, save_mean, save_invstd, gamma, beta, slope, drop_p, dscale, seed, offset, w.partials, Bg, (const uint32_t*)uaps_get_step_state())
-#define UAPS_DX(V, D) hipLaunchKernelGGL((bn_bwd_dx_kernel<V, D>), grid, dim3(kThreads), 0, s, dout, y, dy, C, HW, save_mean, save_invstd, gamma, beta, (const float2*)w.partials, nch, B, dgamma, dbeta, dconv_bias, slope, drop_p, dscale, seed, offset, Bg, (const uint32_t*)uaps_get_step_state(), amax_out)
-    if (vec) { if (drop_p > 0.f) UAPS_SUMS(true, true); else UAPS_SUMS(true, false); }
+#define UAPS_DX(V, D) hipLaunchKernelGGL((bn_bwd_dx_kernel<V, D>), grid, dim3(kThreads), 0, s, dout, y, dy, C, HW, save_mean, save_invstd, gamma, beta, (const float2*)w.partials, nch_p, B, dgamma, dbeta, dconv_bias, slope, drop_p, dscale, seed, offset, Bg, (const uint32_t*)uaps_get_step_state(), amax_out)
+    if (given_partials) {}
+    else if (vec) { if (drop_p > 0.f) UAPS_SUMS(true, true); else UAPS_SUMS(true, false); }
     else { if (drop_p > 0.f) UAPS_SUMS(false, true); else UAPS_SUMS(false, false); }
     if (vec) { if (drop_p > 0.f) UAPS_DX(true, true); else UAPS_DX(true, false); }
     else { if (drop_p > 0.f) UAPS_DX(false, true); else UAPS_DX(false, false); }
@@ -701,6 +708,18 @@ extern "C" int uaps_bn_act_bwd_grouped_h(const uaps_call_hints* hints, const flo
     UAPS_READ_HINTS(hints, h);
     return bn_bwd_impl(h.out_amax, dout, y, gamma, beta, save_mean, save_invstd, slope, drop_p, seed, offset, B, C, H, W, groups, dy, dgamma,
                        dbeta, nullptr, ws, ws_bytes, stream);
+}
+
+// The dx pass alone, from sums the caller already has: partials float2 [C][B][parts_per_image] of (d, d x_hat) as bn_bwd_sums_kernel
+// forms them (uaps_fanin_perturbed_bn_sums).  No dropout; dconv_bias may be NULL.
+extern "C" int uaps_bn_act_bwd_partials_h(const uaps_call_hints* hints, const void* partials, int parts_per_image, const float* dout, const float* y,
+                                          const float* gamma, const float* beta, const float* save_mean, const float* save_invstd, float slope,
+                                          int B, int C, int H, int W, int groups, float* dy, float* dgamma, float* dbeta, float* dconv_bias,
+                                          uaps_stream_t stream) {
+    UAPS_READ_HINTS(hints, h);
+    if (!partials || parts_per_image <= 0) return UAPS_EINVAL;
+    return bn_bwd_impl(h.out_amax, dout, y, gamma, beta, save_mean, save_invstd, slope, 0.f, 0, 0, B, C, H, W, groups, dy, dgamma, dbeta, dconv_bias,
+                       nullptr, 0, stream, (const float2*)partials, parts_per_image);
 }
 
 // The same, also writing the (identically zero) gradient of the bias of the convolution in front of the BatchNorm

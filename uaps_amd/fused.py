@@ -9,10 +9,13 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import _graddest, lazybn, _lib, bounds, stepctx
+from . import _graddest, config, lazybn, _lib, bounds, stepctx
 from . import perturb as _perturb
 
 _ws = _lib.Workspace(min_bytes=1 << 20)
+# The encoder's glue launches folded into their neighbours: the 2x2 max-pool written by the BatchNorm apply pass in front of it, the
+# BatchNorm-backward sums formed by the feature fan-in.  A/B switch; 0 = the separate launches
+ENC_GLUE = config.flag("UAPS_FUSED_ENC_GLUE", True)
 
 # Number of statistics groups of the train-mode BatchNorms: the batch is `_groups()` consecutive blocks, each
 # normalised on its own (UNet_UAPS.forward_pair runs the labelled and the unlabelled batch of a step as one
@@ -48,7 +51,9 @@ class _BnActTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, conv_bias, gamma, beta, running_mean, running_var, nbt, momentum, eps, slope, drop_p, seed, offset,
-                groups=1, stats_partials=None):
+                groups=1, stats_partials=None, feature=0):
+        """feature (an encoder block's last BatchNorm, no dropout, epilogue statistics): 1 leaves a lazybn.BnSource for the feature
+        fan-out in stepctx.fwd().last_bn_source; 2 also has the apply pass write MaxPool2d(2) of the result into it."""
         _lib.require_device(y, "bn_act")
         y = y.contiguous()
         B, Cc, H, W = y.shape
@@ -64,6 +69,11 @@ class _BnActTrain(torch.autograd.Function):
             fn, head = _lib.lib().uaps_bn_act_fwd_train_partials_h, (stats_partials.data_ptr(), int(stats_partials.shape[2]))
         else:
             fn, head = _lib.lib().uaps_bn_act_fwd_train_grouped, ()
+        tail, pooled, idx = (), None, None
+        if feature == 2:
+            pooled = torch.empty((B, Cc, H // 2, W // 2), dtype=torch.float32, device=dev)
+            idx = torch.empty((B, Cc, H // 2, W // 2), dtype=torch.uint8, device=dev)
+            fn, tail = _lib.lib().uaps_bn_act_fwd_train_partials_pool_h, (pooled.data_ptr(), idx.data_ptr())
         with _lib.device_guard(dev):
             if stats_partials is not None:       # hints: the shift the producing conv formed its sums about
                 head = (_lib.mk_hints((), None, (running_mean, conv_bias)) if getattr(stats_partials, "_uaps_shifted", False) else None,) + head
@@ -73,8 +83,10 @@ class _BnActTrain(torch.autograd.Function):
                 running_var.data_ptr() if running_var is not None else None,
                 nbt.data_ptr() if nbt is not None else None, float(momentum), float(eps), float(slope), float(drop_p),
                 seed, offset, B, Cc, H, W, groups, out.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), ws.data_ptr(),
-                ws.numel(), _lib.current_stream(dev))
-        _lib.check(rc, "uaps_bn_act_fwd_train_grouped")
+                ws.numel(), _lib.current_stream(dev), *tail)
+        _lib.check(rc, "uaps_bn_act_fwd_train_partials_pool" if tail else "uaps_bn_act_fwd_train_grouped")
+        if feature:
+            stepctx.fwd().last_bn_source = lazybn.BnSource(out, y, gamma, beta, stats, slope, groups, pooled, idx)
         ctx.save_for_backward(y, gamma, beta, stats)
         ctx.meta = (float(slope), float(drop_p), seed, offset, conv_bias is not None, groups)
         ctx.keys = (id(gamma), id(beta), id(conv_bias) if conv_bias is not None else None)
@@ -84,6 +96,7 @@ class _BnActTrain(torch.autograd.Function):
     def backward(ctx, dout):
         y, gamma, beta, stats = ctx.saved_tensors
         slope, drop_p, seed, offset, has_bias, groups = ctx.meta
+        sums = lazybn.take_sums(dout, y)         # the feature fan-in formed this BatchNorm's sums while it wrote dout: the dx pass alone
         dout = dout.contiguous()
         B, Cc, H, W = y.shape
         dev = y.device
@@ -93,14 +106,21 @@ class _BnActTrain(torch.autograd.Function):
         dgb = [_graddest.take(k, (Cc,), dev) for k in ctx.keys]
         ws = _bn_ws(dev, B, Cc, H, W)
         am = bounds.new_amax(dev) if bounds.enabled() else None      # max|dy|: the operand bound of the convolution's backward
+        hh = _lib.mk_hints((), am) if am is not None else None
         with _lib.device_guard(dev):
-            rc = _lib.lib().uaps_bn_act_bwd_grouped_bias_h(_lib.mk_hints((), am) if am is not None else None, dout.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                                         stats[0].data_ptr(), stats[1].data_ptr(), slope, drop_p, seed, offset, B,
-                                                         Cc, H, W, groups, dy.data_ptr(), dgb[0].data_ptr(), dgb[1].data_ptr(),
-                                                         dgb[2].data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream(dev))
-        _lib.check(rc, "uaps_bn_act_bwd_grouped_bias")
+            if sums is not None:
+                rc = _lib.lib().uaps_bn_act_bwd_partials_h(hh, sums.data_ptr(), int(sums.shape[2]), dout.data_ptr(), y.data_ptr(), gamma.data_ptr(),
+                                                         beta.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), slope, B, Cc, H, W, groups,
+                                                         dy.data_ptr(), dgb[0].data_ptr(), dgb[1].data_ptr(), dgb[2].data_ptr(),
+                                                         _lib.current_stream(dev))
+            else:
+                rc = _lib.lib().uaps_bn_act_bwd_grouped_bias_h(hh, dout.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                                             stats[0].data_ptr(), stats[1].data_ptr(), slope, drop_p, seed, offset, B,
+                                                             Cc, H, W, groups, dy.data_ptr(), dgb[0].data_ptr(), dgb[1].data_ptr(),
+                                                             dgb[2].data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream(dev))
+        _lib.check(rc, "uaps_bn_act_bwd_partials" if sums is not None else "uaps_bn_act_bwd_grouped_bias")
         bounds.put(dy, am)
-        return dy, (dgb[2] if has_bias else None), dgb[0], dgb[1], None, None, None, None, None, None, None, None, None, None, None
+        return dy, (dgb[2] if has_bias else None), dgb[0], dgb[1], None, None, None, None, None, None, None, None, None, None, None, None
 
 
 class _BnAddRelu(torch.autograd.Function):
@@ -214,16 +234,30 @@ class _BnActEval(torch.autograd.Function):
         return dy, None, None, None, None, None, None, None
 
 
+def pool_in_apply(y: torch.Tensor) -> bool:
+    """The BatchNorm apply pass of y has the form that also writes the 2x2 max-pool (uaps_bn_apply_pool_support)."""
+    return y.is_cuda and y.dtype == torch.float32 and _lib.lib().uaps_bn_apply_pool_support(y.shape[2], y.shape[3]) == 0
+
+
 def bn_act(y: torch.Tensor, conv_bias: Optional[torch.Tensor], bn: nn.BatchNorm2d, slope: float, drop_p: float,
-           training: bool, stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+           training: bool, stats: Optional[torch.Tensor] = None, feature: bool = False, pool: bool = False) -> torch.Tensor:
     """dropout_p(leaky_relu(bn(y + conv_bias))) with nn.BatchNorm2d / nn.LeakyReLU / nn.Dropout semantics
-    (UAPS_unet.py:38-40), as three streaming kernels."""
+    (UAPS_unet.py:38-40), as three streaming kernels.
+    feature: the result is an encoder feature map that goes to perturb.perturbed_fan_out; it then carries a lazybn.BnSource
+    (`_uaps_bn_src`) from which the fan's backward forms this BatchNorm's backward sums -- and, with pool, MaxPool2d(2) of the result,
+    written by the apply pass where it has that form (UAPS_FUSED_ENC_GLUE=0: neither)."""
     if training or not bn.track_running_stats:
         p = float(drop_p) if training else 0.0
         seed, off = _perturb.rng().reserve(y.numel()) if p > 0 else (0, 0)
         mom = 0.1 if bn.momentum is None else bn.momentum
+        feat = 0
+        if feature and ENC_GLUE and training and p == 0.0 and stats is not None and y.is_cuda and y.is_contiguous():
+            feat = 2 if (pool and pool_in_apply(y) and y.data_ptr() % 16 == 0) else 1
         out = _BnActTrain.apply(y, conv_bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                                mom, bn.eps, slope, p, seed, off, _groups(), stats)
+                                mom, bn.eps, slope, p, seed, off, _groups(), stats, feat)
+        if feat:
+            f = stepctx.fwd()
+            out._uaps_bn_src, f.last_bn_source = f.last_bn_source, None
         if y.is_cuda and slope <= 1.0:             # |gamma x_hat + beta| <= sqrt(n) max(|gamma| + |beta|), dropout scales by 1 / (1 - p)
             b = bounds.bn_output_bound(bn, y.shape[0] // _groups() * y.shape[2] * y.shape[3], 1.0 / (1.0 - p))
             if b is not None:

@@ -189,6 +189,61 @@ def materialize(dz: torch.Tensor, lz: Lazy) -> torch.Tensor:
     return bounds.put(dy, am)
 
 
+# ---- BatchNorm-backward sums that arrive WITH a gradient (the encoder's feature fan-in forms them, perturb._PerturbFan) -------------
+# Unlike a Lazy record the tensor that carries this one IS the true gradient; the record only spares the BatchNorm node its sums
+# launch.  The fence is the same: version and address at hand-over, counted in the step's scope, an untaken record fails the step.
+_SUMS = "_uaps_bn_sums"
+_sums_handed = 0
+
+
+class BnSource:
+    """What the fan-in needs of the BatchNorm + LeakyReLU (no dropout) that produced a feature map `out` from the raw conv output `y`;
+    `pooled` / `idx`: MaxPool2d(2) of `out` when the apply pass wrote it (csrc/norm_act.hip bn_apply_pool_kernel)."""
+    __slots__ = ("y", "gamma", "beta", "stats", "slope", "groups", "pooled", "idx", "version", "ptr")
+
+    def __init__(self, out, y, gamma, beta, stats, slope, groups, pooled=None, idx=None):
+        self.y, self.gamma, self.beta, self.stats, self.slope, self.groups = y, gamma, beta, stats, float(slope), int(groups)
+        self.pooled, self.idx, self.version, self.ptr = pooled, idx, out._version, out.data_ptr()
+
+    def holds(self, f: torch.Tensor) -> bool:
+        """f is still the tensor the BatchNorm wrote (not modified in place, not a copy)"""
+        return f._version == self.version and f.data_ptr() == self.ptr and f.shape == self.y.shape and f.device == self.y.device
+
+
+class Sums:
+    __slots__ = ("partials", "src", "version", "ptr", "scope")
+
+    def __init__(self, partials, src, version, ptr, scope):
+        self.partials, self.src, self.version, self.ptr, self.scope = partials, src, version, ptr, scope
+
+
+def hand_sums(grad: torch.Tensor, partials: torch.Tensor, src: BnSource, scope: Optional[Scope] = None) -> None:
+    global _sums_handed
+    scope = scope or _loose
+    setattr(grad, _SUMS, Sums(partials, src, grad._version, grad.data_ptr(), scope))
+    scope.outstanding += 1
+    _sums_handed += 1
+
+
+def sums_total() -> int:
+    """Sums records ever handed up (tests)."""
+    return _sums_handed
+
+
+def take_sums(dout: Optional[torch.Tensor], y: torch.Tensor) -> Optional[torch.Tensor]:
+    """The sums partials that came with dout for the BatchNorm whose raw input is y, or None (call before anything that could copy dout)."""
+    rec = getattr(dout, _SUMS, None) if dout is not None else None
+    if rec is None:
+        return None
+    delattr(dout, _SUMS)
+    rec.scope.outstanding = max(0, rec.scope.outstanding - 1)
+    if dout._version != rec.version or dout.data_ptr() != rec.ptr or rec.src.y.data_ptr() != y.data_ptr() or dout.shape != y.shape \
+            or not dout.is_contiguous():
+        raise RuntimeError("a gradient that carries BatchNorm-backward sums was modified, or reached another node than the BatchNorm that "
+                           "produced the feature map (uaps_amd/lazybn.py); set UAPS_FUSED_ENC_GLUE=0")
+    return rec.partials
+
+
 def reset() -> None:
     """Forget what a failed backward may have left behind (records live on their gradient tensors and die with them; only the
     counts remain: the calling thread's open scope and the loose one)."""

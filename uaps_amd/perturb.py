@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, bounds, config, stepctx
+from . import _lib, bounds, config, lazybn, stepctx
 from . import conv as _conv
 
 
@@ -340,10 +340,17 @@ class _PerturbFan(torch.autograd.Function):
     incoming gradient and sums, instead of a backward kernel per perturbation plus a fan-in sum."""
 
     @staticmethod
-    def forward(ctx, f, kinds, groups, noise_range, drop_p, with_pool=False):
+    def forward(ctx, f, kinds, groups, noise_range, drop_p, with_pool=False, src=None):
         ctx.set_materialize_grads(False)
         ctx.step = stepctx.current()       # the trainer scope this forward runs in: the backward starts its early flush (conv.early_flush)
-        f = _prep(f, "perturbed feature fan-out")
+        f_in, f = f, _prep(f, "perturbed feature fan-out")
+        # src (lazybn.BnSource): the BatchNorm that wrote f, whose sole consumer this fan is.  Its apply pass may have written the pooled
+        # map already; inside a trainer's step (lazybn.scope) the backward forms that BatchNorm's backward sums beside the fan-in
+        if src is not None and (f is not f_in or not src.holds(f)):
+            src = None
+        ctx.src = src if (src is not None and lazybn.current() is not None) else None
+        ctx.f, ctx.sums_scope = (f_in, lazybn.current()) if ctx.src is not None else (None, None)
+        have_pool = with_pool and src is not None and src.pooled is not None
         B, Cc, H, W = f.shape
         if B % groups:
             raise ValueError(f"batch {B} is not divisible into {groups} groups")
@@ -380,7 +387,9 @@ class _PerturbFan(torch.autograd.Function):
             with _lib.device_guard(dev):
                 st = _lib.current_stream(dev)
                 pooled = idx = None
-                if with_pool:                # first: the next encoder level waits for this alone
+                if have_pool:                # the BatchNorm's apply pass wrote it (handed out as this node's output: its gradient comes back here)
+                    pooled, idx = src.pooled, src.idx
+                elif with_pool:              # first: the next encoder level waits for this alone
                     pooled = torch.empty((B, Cc, H // 2, W // 2), dtype=torch.float32, device=dev)
                     idx = torch.empty((B, Cc, H // 2, W // 2), dtype=torch.uint8, device=dev)
                     _lib.check(L.uaps_maxpool2x2_fwd(f.data_ptr(), B, Cc, H, W, pooled.data_ptr(), idx.data_ptr(), st), "uaps_maxpool2x2_fwd")
@@ -437,9 +446,12 @@ class _PerturbFan(torch.autograd.Function):
                     raise ValueError(f"unknown perturbation {kind!r}")
                 outs.append(y)
             if with_pool:                    # MaxPool2d(2) of the next DownBlock (UAPS_unet.py:55-58), arg-max kept for the backward
-                pooled = torch.empty((B, Cc, H // 2, W // 2), dtype=torch.float32, device=dev)
-                idx = torch.empty((B, Cc, H // 2, W // 2), dtype=torch.uint8, device=dev)
-                _lib.check(L.uaps_maxpool2x2_fwd(f.data_ptr(), B, Cc, H, W, pooled.data_ptr(), idx.data_ptr(), st), "uaps_maxpool2x2_fwd")
+                if have_pool:
+                    pooled, idx = src.pooled, src.idx
+                else:
+                    pooled = torch.empty((B, Cc, H // 2, W // 2), dtype=torch.float32, device=dev)
+                    idx = torch.empty((B, Cc, H // 2, W // 2), dtype=torch.uint8, device=dev)
+                    _lib.check(L.uaps_maxpool2x2_fwd(f.data_ptr(), B, Cc, H, W, pooled.data_ptr(), idx.data_ptr(), st), "uaps_maxpool2x2_fwd")
                 outs.append(pooled); offsets.append([0] * groups); keeps.append(idx)
         ctx.meta = (tuple(kinds), groups, seed, float(noise_range), float(drop_p), offsets, (B, Cc, H, W), bool(with_pool))
         ctx.keeps = keeps
@@ -451,7 +463,7 @@ class _PerturbFan(torch.autograd.Function):
         modes = [0] + [_KIND_MODE[k] for k in kinds] + ([4] if with_pool else [])
         live = [(g.contiguous(), modes[i], offsets[i], ctx.keeps[i]) for i, g in enumerate(grads) if g is not None]
         if not live:
-            return None, None, None, None, None, None
+            return None, None, None, None, None, None, None
         _conv.early_flush(ctx.step)         # (a training step's scope: the decoders' weight-gradient reductions start beside the encoder's backward)
         if live[0][1] == 4:                 # the output buffer takes its shape from the first entry: keep a full-size one first
             live.append(live.pop(0))
@@ -467,9 +479,20 @@ class _PerturbFan(torch.autograd.Function):
                 md = (C.c_int * n)(*[t[1] for t in live])
                 kp = (C.c_void_p * n)(*[(t[3].data_ptr() if t[3] is not None else None) for t in live])
                 of = (C.c_uint64 * (n * groups))(*[o for t in live for o in t[2]])
+                src = ctx.src
+                if src is not None and not lazybn.observed(ctx.f) and src.y.data_ptr() % 16 == 0 and B * Cc <= 65535:
+                    # also the backward sums of the BatchNorm that wrote f, over (out, its raw input): they travel up on `out`
+                    # (a hook / retain_grad registered on f gets the plain path: the record would not survive autograd's copy)
+                    partials = torch.empty((Cc, B, (H * W + 4095) // 4096, 2), dtype=torch.float32, device=dev)
+                    rc = L.uaps_fanin_perturbed_bn_sums_h(None, gp, md, kp, of, n, groups, seed, rng, p, B, Cc, H, W, out.data_ptr(),
+                                                          src.y.data_ptr(), src.gamma.data_ptr(), src.beta.data_ptr(), src.stats[0].data_ptr(),
+                                                          src.stats[1].data_ptr(), src.slope, partials.data_ptr(), st)
+                    _lib.check(rc, "uaps_fanin_perturbed_bn_sums")
+                    lazybn.hand_sums(out, partials, src, ctx.sums_scope)
+                    return out, None, None, None, None, None, None
                 _lib.check(L.uaps_fanin_perturbed(gp, md, kp, of, n, groups, seed, rng, p, B, Cc, H, W, out.data_ptr(), st),
                            "uaps_fanin_perturbed")
-                return out, None, None, None, None, None
+                return out, None, None, None, None, None, None
             if any(t[1] == 4 for t in live):
                 raise _lib.UapsHipError("fused max-pool backward needs H*W % 4 == 0 and 16-byte aligned gradients")
             # general shapes: one backward kernel per perturbation, then the plain fan-in sum
@@ -496,16 +519,22 @@ class _PerturbFan(torch.autograd.Function):
                 ptrs = (C.c_void_p * len(chunk))(*[t.data_ptr() for t in chunk])
                 _lib.check(L.uaps_sum_tensors(ptrs, len(chunk), out.data_ptr(), out.numel(), st), "uaps_sum_tensors")
                 acc = [out] + acc
-            return (out if len(parts) > 1 else parts[0]), None, None, None, None, None
+            return (out if len(parts) > 1 else parts[0]), None, None, None, None, None, None
 
 
 def perturbed_fan_out(f: torch.Tensor, kinds, groups: int = 1, noise_range: float = 0.3, drop_p: float = 0.5,
-                      with_pool: bool = False):
+                      with_pool: bool = False, sole_consumer: bool = False):
     """[f, P_1(f), ..., P_n(f)] for kinds in {"noise", "dropout", "feature_dropout"} (one entry per auxiliary decoder);
-    with_pool appends MaxPool2d(2)(f), whose gradient returns through the same fused backward kernel."""
+    with_pool appends MaxPool2d(2)(f), whose gradient returns through the same fused backward kernel.
+    sole_consumer: the caller uses f nowhere else -- the fan's gradient is then all of f's, and where f carries the record of the
+    BatchNorm that wrote it (fused.bn_act feature=True) the pooled map comes from that BatchNorm's apply pass and the fan-in kernel
+    forms its backward sums."""
     if with_pool and (f.shape[2] % 2 or f.shape[3] % 8):
         raise ValueError("with_pool needs an even height and a width that is a multiple of 8")
-    outs = _PerturbFan.apply(f, tuple(kinds), int(groups), noise_range, drop_p, bool(with_pool))
+    src = getattr(f, "_uaps_bn_src", None) if sole_consumer else None
+    if src is not None and (lazybn.observed(f) or not f.requires_grad):
+        src = None
+    outs = _PerturbFan.apply(f, tuple(kinds), int(groups), noise_range, drop_p, bool(with_pool), src)
     if bounds.get(f) is not None:            # |f (1 + U(-r, r))| <= (1 + r) |f|, dropout scales by 1 / (1 - p), masks and max-pool contract
         factor = {"noise": 1.0 + abs(float(noise_range)), "dropout": 1.0 / (1.0 - float(drop_p)), "feature_dropout": 1.0}
         fs = [1.0] + [factor[k] for k in kinds] + ([1.0] if with_pool else [])

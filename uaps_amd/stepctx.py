@@ -44,6 +44,7 @@ class _Forward(threading.local):
         self.amax_request = False                # conv.request_out_amax(): the next forward convolution raises a bound to max|its output|
         self.last_out_amax = None
         self.last_up2x_amax = None               # fused.upsample2x: the bound of the tensor it just wrote
+        self.last_bn_source = None               # fused._BnActTrain: the lazybn.BnSource of the feature map it just wrote
         self.stat_groups = 1                     # fused.stat_groups(n)
         self.fan_side = None                     # perturb: the stream the perturbed feature copies are written on (None: the caller's)
         self.lazy_scope = None                   # lazybn.scope(): the innermost open scope object

@@ -57,8 +57,11 @@ class ConvBlock(nn.Module):
                   nn.LeakyReLU(LEAKY_SLOPE)]
         self.conv_conv = nn.Sequential(*layers)      # indices 0,1,4,5 carry the parameters
 
-    def forward(self, x: torch.Tensor, x2: Optional[torch.Tensor] = None, lazy: bool = False, x2_low: bool = False):
-        """x2: second half of a channel concatenation [x, x2] that is not materialised (GPU only).
+    def forward(self, x: torch.Tensor, x2: Optional[torch.Tensor] = None, lazy: bool = False, x2_low: bool = False,
+                feature: Optional[str] = None):
+        """feature: the result is an encoder feature map whose only consumer is perturb.perturbed_fan_out(sole_consumer=True) --
+        "fan", or "pool" when that fan also wants its 2x2 max-pool (fused.bn_act; train mode on the GPU only).
+        x2: second half of a channel concatenation [x, x2] that is not materialised (GPU only).
         x2_low: x2 is the LOW-resolution tensor; the first convolution's kernels up-sample it x2 while staging (conv.conv2d_cat up2).
         lazy: the caller feeds the result to exactly one convolution and can apply the last BatchNorm + LeakyReLU there
         (fused.bn_act_conv); then a PendingBnAct may come back instead of a tensor (train mode on the GPU only)."""
@@ -77,10 +80,10 @@ class ConvBlock(nn.Module):
                 y, st = fused.bn_act_conv(y, st, c0.bias, b0, LEAKY_SLOPE, c1.weight, None, want_stats=True, stat_shift=sh1)
                 if lazy and y.shape[1] > 4:
                     return PendingBnAct(y, st, c1.bias, b1)
-                return fused.bn_act(y, c1.bias, b1, LEAKY_SLOPE, 0.0, True, st)
+                return fused.bn_act(y, c1.bias, b1, LEAKY_SLOPE, 0.0, True, st, feature=feature is not None, pool=feature == "pool")
             a = fused.bn_act(y, c0.bias, b0, LEAKY_SLOPE, d0.p, True, st)
             y, st = conv.conv2d_with_stats(a, c1.weight, None, stat_shift=sh1)
-            return fused.bn_act(y, c1.bias, b1, LEAKY_SLOPE, 0.0, True, st)
+            return fused.bn_act(y, c1.bias, b1, LEAKY_SLOPE, 0.0, True, st, feature=feature is not None, pool=feature == "pool")
         y = conv.conv2d(x, c0.weight, None) if x2 is None else conv.conv2d_cat(x, x2, c0.weight, None, up2=x2_low)
         a = fused.bn_act(y, c0.bias, b0, LEAKY_SLOPE, d0.p, self.training)
         return fused.bn_act(conv.conv2d(a, c1.weight, None), c1.bias, b1, LEAKY_SLOPE, 0.0, self.training)
@@ -405,17 +408,26 @@ class UNet_UAPS(nn.Module):
                 if self._fan_stream is None or self._fan_stream.device != x.device:
                     self._fan_stream = torch.cuda.Stream(device=x.device)
                 fan_side = self._fan_stream
-            fans, f = [], enc.in_conv(x)
+            def pools(h, w):
+                # (the fan-in kernel sums at most 8 gradients: clean + n_aux perturbed + the pooled one)
+                return _FUSED_POOL and h % 2 == 0 and w % 8 == 0 and self.n_aux + 2 <= 8
+
+            # a level's feature map goes to its fan alone when the fan also pools it (or nothing follows): the block that writes it is
+            # told, so that its last BatchNorm can write the pooled map and leave the fan-in its backward sums (fused.bn_act)
+            blocks = (enc.down1, enc.down2, enc.down3, enc.down4, None)
+            fans, f = [], enc.in_conv(x, feature="pool" if pools(x.shape[2], x.shape[3]) else None)
             stepctx.fwd().fan_side = fan_side
             try:
-                for blk in (enc.down1, enc.down2, enc.down3, enc.down4, None):
-                    # (the fan-in kernel sums at most 8 gradients: clean + n_aux perturbed + the pooled one)
-                    pool = blk is not None and _FUSED_POOL and f.shape[2] % 2 == 0 and f.shape[3] % 8 == 0 and self.n_aux + 2 <= 8
+                for i, blk in enumerate(blocks):
+                    pool = blk is not None and pools(f.shape[2], f.shape[3])
                     fan = perturb.perturbed_fan_out(f, kinds, _groups, self._noise.uniform_range, drop_p=self.aux_dropout_p,
-                                                    with_pool=pool)
+                                                    with_pool=pool, sole_consumer=pool or blk is None)
                     fans.append(fan)
-                    if blk is not None:
-                        f = blk.maxpool_conv[1](fan[-1]) if pool else blk(f)
+                    if blk is not None and pool:
+                        nxt = "fan" if blocks[i + 1] is None else ("pool" if pools(fan[-1].shape[2], fan[-1].shape[3]) else None)
+                        f = blk.maxpool_conv[1](fan[-1], feature=nxt)
+                    elif blk is not None:
+                        f = blk(f)
             finally:
                 stepctx.fwd().fan_side = None
             if fan_side is not None:

@@ -1930,6 +1930,73 @@ typedef struct uaps_hull_call {
 int uaps_hull_workspace_bytes(int B, int H, int W, int max_instances, size_t* bytes);
 int uaps_hull_descriptors(const uaps_hull_call* call);
 
+/* ---------------------------------------------------------------------------------------------
+ * Defect contours: csrc/contours.hip.
+ *
+ * uaps_contours_trace / uaps_contours_write: the boundary of every component of the `labels` of uaps_label_instances as closed
+ *   rings of corner-lattice points, outer rings and hole rings, exact integers.
+ *   labels int32 [B, H, W]: 0 = no component, k >= 1 = component k of that image.
+ *   Geometry.  A pixel (y, x) is the closed unit square [x, x + 1] x [y, y + 1]; ring points lie on the corner lattice 0..H x 0..W
+ *   and are stored (y, x).  For a label k, 1 <= k <= max_instances, every unit side between a pixel of k and anything else (another
+ *   label, 0, a label outside [1, max_instances], the frame) is a directed edge with k on its right; directions E, S, W, N = 0..3:
+ *     top side of (y, x): from (y, x) heading E;          right side: from (y, x + 1) heading S;
+ *     bottom side:        from (y + 1, x + 1) heading W;  left side:  from (y + 1, x) heading N.
+ *   Outer rings run clockwise on the screen (as the hull does), hole rings counter-clockwise.  The next edge leaves the end vertex
+ *   of this one; it is unique but at a saddle vertex (k on exactly the two diagonal pixels of the 2 x 2 window), where
+ *   connectivity 8 turns left (d + 3 mod 4: the diagonal pixels stay on one ring) and connectivity 4 right (d + 1).  A ring is one
+ *   cycle of that map.  It starts at its smallest vertex (y, then x), which it visits once: outer rings leave it heading E, hole
+ *   rings heading S.  Rings are ordered by (image, start y, start x, direction of the start edge) -- a raster order, not grouped
+ *   by label.
+ *     points       int32 [N, 2]   the start vertices (y, x) of the edges whose direction differs from their predecessor's, ring after
+ *                                 ring, from the ring's start; the first point is not repeated.  Even and >= 4 a ring; a saddle
+ *                                 vertex can occur twice
+ *     ring_offsets int32 [L + 1]  ring r owns points[ring_offsets[r] .. ring_offsets[r + 1])
+ *     rings        int64 [L, 7]   image, label, start y, start x, points, length (unit edges), area2 (the shoelace sum
+ *                                 x y' - x' y over the edges: twice the enclosed area, > 0 for outer rings, < 0 for holes)
+ *     summary      int64 [B, max_instances, 4]   per label the sums over its rings: rings, points, perimeter (= sum of length),
+ *                                 area2 (= twice the label's pixel count); zero rows for labels without a pixel
+ *     totals       int64 [4]      L, N, the doubling rounds that ran, the number of directed edges
+ *   uaps_contours_trace fills the workspace, `summary` and `totals` (on the device); it does not synchronise.  The caller reads
+ *   L and N from `totals`, provides points / ring_offsets / rings of at least that capacity and passes both the totals it read
+ *   (n_rings, n_points) and the capacities to uaps_contours_write, which fills them from the SAME, untouched workspace with one
+ *   launch.  With L = 0 there is nothing to write (n_rings < 1 is refused).  A workspace whose totals are not the ones passed
+ *   makes the launch store nothing.  Every output word is written once, whatever outputs and workspace held before; the same
+ *   bits from run to run; no float is used.
+ *   Passes: a scan of per-vertex edge counts compacts the edges in key order (image, start vertex, direction); every edge names
+ *   its successor from the 2 x 2 window at its end vertex; pointer doubling along the predecessors, one launch a round (at most
+ *   ceil(log2(4 H W)); a launch returns at once after a round that changed nothing, without a host read), gives every edge its
+ *   ring's smallest edge and its rank from it; two more scans give ring indices, point slots and the shoelace sums.
+ *   workspace: uaps_contours_workspace_bytes(B, H, W, max_instances): about 192 bytes a pixel and 4 a lattice vertex, 256-byte
+ *   aligned, the pair of calls' alone from trace until write has run; it need not be zeroed.
+ * Errors (nothing launched, outputs untouched): UAPS_EINVAL null struct, labels or workspace, trace: null summary or totals or two
+ *   of labels / summary / totals equal, write: null points, ring_offsets or rings, n_rings < 1, n_points < 4, a total of 2^31 or
+ *   more, ring_capacity < n_rings or point_capacity < n_points; non-positive dimension, max_instances < 1, connectivity not 4 or
+ *   8, struct_size below this version's (the query: a NULL result pointer); UAPS_ERANGE H or W above UAPS_CONTOUR_MAX_EXTENT,
+ *   B * H * W * 32 >= 2 GiB (every workspace array stays below 2 GiB), a summary of 2 GiB or more; UAPS_EWORKSPACE a workspace
+ *   smaller than the query's answer or not 256-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_CONTOUR_COLUMNS 4
+#define UAPS_CONTOUR_RING_COLUMNS 7
+#define UAPS_CONTOUR_MAX_EXTENT 4096
+typedef struct uaps_contour_call {
+    uint32_t struct_size;
+    int32_t B, H, W, max_instances, connectivity;
+    const int32_t* labels;                       /* [B][H][W] */
+    int64_t* summary;                            /* trace: [B][max_instances][4], written whole */
+    int64_t* totals;                             /* trace: [4] on the device */
+    int64_t n_rings, n_points;                   /* write: L and N as read from totals */
+    int64_t ring_capacity, point_capacity;       /* write: rows of rings (ring_offsets has one more) and of points */
+    int32_t* points;                             /* write: [point_capacity][2] */
+    int32_t* ring_offsets;                       /* write: [ring_capacity + 1] */
+    int64_t* rings;                              /* write: [ring_capacity][7] */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_contour_call;
+int uaps_contours_workspace_bytes(int B, int H, int W, int max_instances, size_t* bytes);
+int uaps_contours_trace(const uaps_contour_call* call);
+int uaps_contours_write(const uaps_contour_call* call);
+
 #ifdef __cplusplus
 }
 #endif

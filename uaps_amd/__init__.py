@@ -58,6 +58,11 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
                                                     farthest pair, minimum caliper width and minimum-area rectangle as exact
                                                     integers; HullResult.props(): solidity, Feret diameters, the rotated box;
                                                     inference.predict_instances(..., hull=True)
+  contours, ContourResult, RING_COLUMNS, CONTOUR_COLUMNS
+                                                    defect contours from the labels of label_instances: crack-following outer and
+                                                    hole rings as closed polygons of corner-lattice points, exact integers;
+                                                    ContourResult.polygons(), records(), to_coco();
+                                                    inference.predict_instances(..., contours=True)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -99,6 +104,7 @@ from .skeleton import skeletonize, skeleton_descriptors, SkeletonResult, Skeleto
 from . import skeleton
 from .hull import hull_descriptors, HullResult, HULL_COLUMNS
 from . import hull
+from .contours import contours, ContourResult, RING_COLUMNS, CONTOUR_COLUMNS      # (the function takes the submodule's name)
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -195,6 +195,9 @@ SIGNATURES = {
     "uaps_plane_curves": (C.c_int, [_PTR]),
     "uaps_hull_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
     "uaps_hull_descriptors": (C.c_int, [_PTR]),
+    "uaps_contours_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
+    "uaps_contours_trace": (C.c_int, [_PTR]),
+    "uaps_contours_write": (C.c_int, [_PTR]),
 }
 
 
@@ -437,6 +440,18 @@ class HullCall(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("max_instances", C.c_int32),
                 ("labels", C.c_void_p), ("table", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
                 ("stream", C.c_void_p)]
+
+
+CONTOUR_COLUMNS, CONTOUR_RING_COLUMNS, CONTOUR_MAX_EXTENT = 4, 7, 4096     # UAPS_CONTOUR_COLUMNS, _RING_COLUMNS, _MAX_EXTENT
+
+
+class ContourCall(C.Structure):
+    """uaps_contour_call (include/uaps_hip.h): every operand of uaps_contours_trace and uaps_contours_write, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("max_instances", C.c_int32),
+                ("connectivity", C.c_int32), ("labels", C.c_void_p), ("summary", C.c_void_p), ("totals", C.c_void_p),
+                ("n_rings", C.c_int64), ("n_points", C.c_int64), ("ring_capacity", C.c_int64), ("point_capacity", C.c_int64),
+                ("points", C.c_void_p), ("ring_offsets", C.c_void_p), ("rings", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
 TILE_MAX_CHUNKS, TILE_MAX_MAPS = 32, 2  # UAPS_TILE_MAX_CHUNKS, UAPS_TILE_MAX_MAPS

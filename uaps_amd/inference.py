@@ -247,7 +247,8 @@ def _with_shapes(inst, shapes, connectivity: int):
 
 @torch.no_grad()
 def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, tiled=None, min_area: int = 1, connectivity: int = 8,
-                      max_instances: int = 256, cleanup=None, components=None, shapes=False, skeleton=False, hull=False):
+                      max_instances: int = 256, cleanup=None, components=None, shapes=False, skeleton=False, hull=False,
+                      contours=False):
     """Defects instead of pixels: instances.label_instances on the main head's arg-max mask, with maps = (confidence, uncertainty).
     The confidence is the main head's largest softmax; with tta (True, or a tuple of scales) mask and confidence are those of
     tta.predict_tta.  The uncertainty is consistency.uncertainty_map(main, aux1) of the plain forward where the model has an auxiliary
@@ -265,8 +266,14 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     and records() merges both.  Under all three paths.
     hull=True: a hull.HullResult instead -- hull.hull_descriptors of that InstanceResult; its `.also` holds what the same call returns
     without hull= (the ShapeResult, the SkeletonStats, or None for the bare InstanceResult), and its props() and records() add
-    solidity, the Feret diameters and the minimum-area rectangle to every defect.  Under all three paths."""
+    solidity, the Feret diameters and the minimum-area rectangle to every defect.  Under all three paths.
+    contours=True: a contours.ContourResult instead -- contours.contours of that InstanceResult at the call's connectivity: the
+    boundary of every defect as polygon rings (polygons(), to_coco()); its `.also` holds what the same call returns without
+    contours= (the HullResult, the ShapeResult, the SkeletonStats, or None for the bare InstanceResult) and its records() adds
+    the ring counts and the crack perimeter to theirs.  Under all three paths, after both clean-up chains."""
     from . import instances
+    if contours is not False and contours is not True:
+        raise ValueError("predict_instances: contours is False or True")
     if hull is not False and hull is not True:
         raise ValueError("predict_instances: hull is False or True")
     if shapes not in (False, True, "thickness"):
@@ -298,10 +305,13 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
         skel = skeletonize(mask, num_classes, **(skeleton if isinstance(skeleton, dict) else {}))
         stats = skeleton_descriptors(inst, skel)
         res = stats._replace(shapes=_with_shapes(inst, shapes, connectivity)) if shapes else stats
-    if not hull:
+    if hull:
+        from .hull import hull_descriptors
+        res = hull_descriptors(inst)._replace(also=None if res is inst else res)
+    if not contours:
         return res
-    from .hull import hull_descriptors
-    return hull_descriptors(inst)._replace(also=None if res is inst else res)
+    from .contours import contours as trace_contours
+    return trace_contours(inst, connectivity)._replace(also=None if res is inst else res)
 
 
 def load_for_inference(model: torch.nn.Module, checkpoint_path: str, device: Optional[torch.device] = None) -> Dict:

@@ -1997,6 +1997,78 @@ int uaps_contours_workspace_bytes(int B, int H, int W, int max_instances, size_t
 int uaps_contours_trace(const uaps_contour_call* call);
 int uaps_contours_write(const uaps_contour_call* call);
 
+/* ---------------------------------------------------------------------------------------------
+ * Contour simplification: csrc/simplify.hip.
+ *
+ * uaps_contours_simplify_mark / uaps_contours_simplify_write: exact Ramer-Douglas-Peucker on the rings of uaps_contours_write;
+ *   integers only, the same bits from run to run and from every kernel form.
+ *   Inputs: points int32 [n_points, 2] (y, x), coordinates in 0 .. UAPS_CONTOUR_MAX_EXTENT; ring_offsets int32 [n_rings + 1];
+ *   rings int64 [n_rings, 7]; summary_in int64 [B, max_instances, 4] -- the outputs of uaps_contours_trace / _write.
+ *   A ring has n >= 4 points p_0 .. p_{n-1}; index n means p_0 again.  e16 is the tolerance in sixteenths of a pixel, 0 .. 1024.
+ *   Deviation of P from the SEGMENT A -> B as a fraction num / den of squared pixels, d = B - A, L2 = |d|^2, t = (P - A) . d:
+ *     L2 == 0: num = |P - A|^2, den = 1;   t <= 0: num = |P - A|^2 L2, den = L2;   t >= L2: num = |P - B|^2 L2, den = L2;
+ *     otherwise num = cross(d, P - A)^2, den = L2.            (num <= 2^50: every comparison stays inside int64)
+ *   P exceeds the tolerance where 256 num > e16^2 den (strict).
+ *   Split rule, for an interval (i, j) of kept indices with j > i + 1: the interior index k with the largest num (den is common),
+ *   the lowest k among the equal; if it exceeds the tolerance k is kept and the rule goes on in (i, k) and (k, j), otherwise
+ *   nothing inside is kept.  A ring keeps 0 and b, the index with the largest |p_i - p_0|^2 (the lowest among the equal), and runs
+ *   the rule on (0, b) and (b, n).  If neither splits, the index with the largest num over both (they share the segment; the
+ *   lowest among the equal) is kept all the same and the rule goes on in its two halves: a ring never falls below a triangle, and
+ *   every dropped point stays within the tolerance of the segment between the kept points that bracket it.
+ *   NOT promised: a simplified ring may touch or cross itself or another ring, and the sign of its own area can change.
+ *     points_out       int32 [N', 2]           the kept points in source order, ring after ring, p_0 first
+ *     ring_offsets_out int32 [n_rings + 1]
+ *     rings_out        int64 [n_rings, 7]      the source rows with column `points` = the kept count; length and area2 stay the
+ *                                              traced ring's
+ *     ring_stats       int64 [n_rings, 2]      points of the source ring, the shoelace sum of the simplified ring
+ *     summary_out      int64 [B, max_instances, 4]   summary_in with kept - n of every ring added to column `points`
+ *     totals           int64 [4]               n_rings, N', the rings that took the LDS form, the rings that took the global form
+ *   uaps_contours_simplify_mark copies the summary, runs the split rule, counts and scans the kept points and fills `totals` (on
+ *   the device); it does not synchronise.  The caller reads N' from `totals`, provides the outputs and passes n_points_out = N' and
+ *   the capacities to uaps_contours_simplify_write, which fills them from the SAME, untouched workspace with one launch.  A
+ *   workspace whose total is not the one passed makes the launch store nothing.
+ *   Forms, by a ring's point count n: n <= wave_max one ring a wave (a point a lane); n <= lds_max one ring a workgroup with its
+ *   state in LDS; any n one ring a workgroup with its state in the workspace.  wave_max / lds_max: 0 = the default
+ *   (UAPS_SIMPLIFY_WAVE_MAX, UAPS_SIMPLIFY_LDS_MAX), UAPS_SIMPLIFY_OFF = no ring takes the form; they change the time, never a bit.
+ *   workspace: uaps_contours_simplify_workspace_bytes(n_points, n_rings): about 28 bytes a point and 24 a ring, 256-byte aligned,
+ *   the pair of calls' alone from mark until write has run; it need not be zeroed.
+ * Errors (nothing launched, outputs untouched): UAPS_EINVAL null struct, points, ring_offsets, rings or workspace, B or
+ *   max_instances < 1, n_points or n_rings < 1, e16 outside 0 .. UAPS_SIMPLIFY_MAX_E16, wave_max / lds_max above the form's capacity
+ *   or below UAPS_SIMPLIFY_OFF, struct_size below this version's, mark: null summary_in, summary_out or totals or two of them equal,
+ *   write: a null output, n_points_out < 1 or above n_points, ring_capacity < n_rings or point_capacity < n_points_out;
+ *   UAPS_ERANGE n_points of 2^30 or more, more rings than points, a summary of 2 GiB or more; UAPS_EWORKSPACE a workspace smaller
+ *   than the query's answer or not 256-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_SIMPLIFY_WAVE_MAX 64
+#define UAPS_SIMPLIFY_LDS_MAX 2048
+#define UAPS_SIMPLIFY_MAX_E16 1024
+#define UAPS_SIMPLIFY_OFF (-1)
+typedef struct uaps_simplify_call {
+    uint32_t struct_size;
+    int32_t B, max_instances;                    /* the summary's rows */
+    int32_t e16;
+    int32_t wave_max, lds_max;
+    int64_t n_points, n_rings;
+    const int32_t* points;                       /* [n_points][2] */
+    const int32_t* ring_offsets;                 /* [n_rings + 1] */
+    const int64_t* rings;                        /* [n_rings][7] */
+    const int64_t* summary_in;                   /* mark: [B][max_instances][4] */
+    int64_t* summary_out;                        /* mark: [B][max_instances][4], written whole */
+    int64_t* totals;                             /* mark: [4] on the device */
+    int64_t n_points_out;                        /* write: N' as read from totals */
+    int64_t ring_capacity, point_capacity;       /* write: rows of rings_out and ring_stats (ring_offsets_out has one more), of points_out */
+    int32_t* points_out;                         /* write: [point_capacity][2] */
+    int32_t* ring_offsets_out;                   /* write: [ring_capacity + 1] */
+    int64_t* rings_out;                          /* write: [ring_capacity][7] */
+    int64_t* ring_stats;                         /* write: [ring_capacity][2] */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_simplify_call;
+int uaps_contours_simplify_workspace_bytes(int64_t n_points, int64_t n_rings, size_t* bytes);
+int uaps_contours_simplify_mark(const uaps_simplify_call* call);
+int uaps_contours_simplify_write(const uaps_simplify_call* call);
+
 #ifdef __cplusplus
 }
 #endif

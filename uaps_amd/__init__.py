@@ -63,6 +63,9 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
                                                     hole rings as closed polygons of corner-lattice points, exact integers;
                                                     ContourResult.polygons(), records(), to_coco();
                                                     inference.predict_instances(..., contours=True)
+  simplify_contours, SimplifiedContours             contour simplification: exact Ramer-Douglas-Peucker on those rings at a tolerance
+                                                    in sixteenths of a pixel, integers only; polygons(), records(), to_coco(),
+                                                    reduction(); inference.predict_instances(..., contours=True, simplify=epsilon)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -105,6 +108,8 @@ from . import skeleton
 from .hull import hull_descriptors, HullResult, HULL_COLUMNS
 from . import hull
 from .contours import contours, ContourResult, RING_COLUMNS, CONTOUR_COLUMNS      # (the function takes the submodule's name)
+from .simplify import simplify_contours, SimplifiedContours
+from . import simplify
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -198,6 +198,9 @@ SIGNATURES = {
     "uaps_contours_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
     "uaps_contours_trace": (C.c_int, [_PTR]),
     "uaps_contours_write": (C.c_int, [_PTR]),
+    "uaps_contours_simplify_workspace_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
+    "uaps_contours_simplify_mark": (C.c_int, [_PTR]),
+    "uaps_contours_simplify_write": (C.c_int, [_PTR]),
 }
 
 
@@ -452,6 +455,19 @@ class ContourCall(C.Structure):
                 ("n_rings", C.c_int64), ("n_points", C.c_int64), ("ring_capacity", C.c_int64), ("point_capacity", C.c_int64),
                 ("points", C.c_void_p), ("ring_offsets", C.c_void_p), ("rings", C.c_void_p), ("workspace", C.c_void_p),
                 ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+SIMPLIFY_WAVE_MAX, SIMPLIFY_LDS_MAX, SIMPLIFY_MAX_E16, SIMPLIFY_OFF = 64, 2048, 1024, -1     # UAPS_SIMPLIFY_*
+
+
+class SimplifyCall(C.Structure):
+    """uaps_simplify_call (include/uaps_hip.h): every operand of uaps_contours_simplify_mark and _write, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("max_instances", C.c_int32), ("e16", C.c_int32),
+                ("wave_max", C.c_int32), ("lds_max", C.c_int32), ("n_points", C.c_int64), ("n_rings", C.c_int64),
+                ("points", C.c_void_p), ("ring_offsets", C.c_void_p), ("rings", C.c_void_p), ("summary_in", C.c_void_p),
+                ("summary_out", C.c_void_p), ("totals", C.c_void_p), ("n_points_out", C.c_int64), ("ring_capacity", C.c_int64),
+                ("point_capacity", C.c_int64), ("points_out", C.c_void_p), ("ring_offsets_out", C.c_void_p), ("rings_out", C.c_void_p),
+                ("ring_stats", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
 TILE_MAX_CHUNKS, TILE_MAX_MAPS = 32, 2  # UAPS_TILE_MAX_CHUNKS, UAPS_TILE_MAX_MAPS

@@ -248,7 +248,7 @@ def _with_shapes(inst, shapes, connectivity: int):
 @torch.no_grad()
 def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, tiled=None, min_area: int = 1, connectivity: int = 8,
                       max_instances: int = 256, cleanup=None, components=None, shapes=False, skeleton=False, hull=False,
-                      contours=False):
+                      contours=False, simplify=None):
     """Defects instead of pixels: instances.label_instances on the main head's arg-max mask, with maps = (confidence, uncertainty).
     The confidence is the main head's largest softmax; with tta (True, or a tuple of scales) mask and confidence are those of
     tta.predict_tta.  The uncertainty is consistency.uncertainty_map(main, aux1) of the plain forward where the model has an auxiliary
@@ -270,10 +270,18 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     contours=True: a contours.ContourResult instead -- contours.contours of that InstanceResult at the call's connectivity: the
     boundary of every defect as polygon rings (polygons(), to_coco()); its `.also` holds what the same call returns without
     contours= (the HullResult, the ShapeResult, the SkeletonStats, or None for the bare InstanceResult) and its records() adds
-    the ring counts and the crack perimeter to theirs.  Under all three paths, after both clean-up chains."""
+    the ring counts and the crack perimeter to theirs.  Under all three paths, after both clean-up chains.
+    simplify=epsilon (a float, pixels; needs contours=True): a simplify.SimplifiedContours instead -- simplify.simplify_contours of
+    that ContourResult at the tolerance epsilon, the staircases of slanted edges reduced to their corners; its `.source` is the
+    ContourResult.  Under all three paths."""
     from . import instances
     if contours is not False and contours is not True:
         raise ValueError("predict_instances: contours is False or True")
+    if simplify is not None:
+        from .simplify import quantise
+        if not contours:
+            raise ValueError("predict_instances: simplify needs contours=True")
+        quantise(simplify)
     if hull is not False and hull is not True:
         raise ValueError("predict_instances: hull is False or True")
     if shapes not in (False, True, "thickness"):
@@ -311,7 +319,11 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     if not contours:
         return res
     from .contours import contours as trace_contours
-    return trace_contours(inst, connectivity)._replace(also=None if res is inst else res)
+    traced = trace_contours(inst, connectivity)._replace(also=None if res is inst else res)
+    if simplify is None:
+        return traced
+    from .simplify import simplify_contours
+    return simplify_contours(traced, simplify)
 
 
 def load_for_inference(model: torch.nn.Module, checkpoint_path: str, device: Optional[torch.device] = None) -> Dict:

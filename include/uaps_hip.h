@@ -1792,6 +1792,73 @@ int uaps_match_workspace_bytes(int B, int max_pred, int max_gt, size_t* bytes);
 int uaps_match_instances(const uaps_match_call* call);
 
 /* ---------------------------------------------------------------------------------------------
+ * Defect detection matching over an IoU sweep: csrc/detect.hip.  The COCO assignment step on the pair matrix of uaps_match_instances
+ * (same pixel rule, csrc/pair_count.hpp): per image, class and threshold the detections are visited in score order and each takes the
+ * not-yet-taken ground-truth defect of largest IoU among those that pass.  Integers throughout (the score key aside), no float compare
+ * of IoUs anywhere.
+ *
+ *   Thresholds   T of them (1 <= T <= UAPS_DETECT_MAX_THRESHOLDS), integers per mille, strictly ascending, each in [100, 1000].
+ *   IoU test     1000 * inter >= t1000 * (area_p + area_g - inter), in 64-bit integers; two IoUs are compared by cross-multiplication.
+ *   Score key    scores == NULL: (double) sum0 / (double) area of the prediction's table row (one correctly rounded division; the
+ *                2^-24 scale of the fixed-point sum is left to whoever shows the score); else scores[b][p].  -0 counts as +0.  A NaN
+ *                orders after every number and is written as -inf; rows without a defect hold -inf.
+ *   Groups       a defect takes part iff it has a table row and its class lies in [0, num_classes); with class_agnostic == 1 every
+ *                defect with a row takes part as class 0.  Within an (image, class) detections are ordered by key descending, the lower
+ *                number first on ties; with max_dets = n > 0 only the first n of each (image, class) take part (0: all of them).
+ *   Greedy rule  per image, class and threshold, in that order: a detection takes the free ground-truth defect of largest IoU among
+ *                those passing the test (the lowest number on ties); a ground-truth defect is taken at most once per threshold.
+ *     score      double [B, max_pred]
+ *     rank       int64 [B, max_pred]: position within the (image, class), -1 for rows that take no part
+ *     pred_match int64 [B, max_pred, T]: the ground-truth number taken, 0: none;  pred_inter: int64 [B, max_pred, T], its intersection
+ *     target_match int64 [B, max_gt, T]: the detection number, 0: none
+ *     counts     int64 [B, num_classes, T + 2]: tp per threshold, n_pred taking part, n_gt
+ *   Launches: the two of the pair count; candidates (one wave per (b, p): the at most UAPS_DETECT_MAX_CANDIDATES = 10 ground-truth
+ *   defects that pass the lowest threshold -- inter >= t_min union >= t_min area_p and ground-truth defects are disjoint -- ordered by
+ *   (IoU descending, number ascending), and the score key); order (one workgroup per image: rank by counting inside the class, the
+ *   class-major sequence, n_pred and n_gt); sweep (one wave per image, lane = threshold, detections in sequence; taken-masks in LDS).
+ *   Integer atomics only in the pair count, no workgroup waits for another: two runs give the same bits.  The call does not synchronise.
+ *   workspace: uaps_detect_workspace_bytes(B, max_pred, max_gt, T) bytes, 256-byte aligned, the call's alone until it has run.
+ * The struct is size-versioned (fields are only ever appended; a larger struct_size is accepted and what it appends is not read).
+ * Errors (nothing launched): UAPS_EINVAL null struct or pointer (scores may be null), non-positive dimension or max_pred / max_gt,
+ *   struct_size below this version's, class_agnostic outside {0, 1}, negative max_dets, a workspace that is too small or not 256-byte
+ *   aligned; UAPS_ERANGE T outside [1, UAPS_DETECT_MAX_THRESHOLDS], a threshold outside [100, 1000] or not above the one before it,
+ *   num_classes outside [1, UAPS_MATCH_MAX_CLASSES], max_pred or max_gt above UAPS_DETECT_MAX_ROWS, H * W >= 2^31, a pair matrix of
+ *   B * max_pred * max_gt * 4 bytes at or beyond 2 GiB.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_DETECT_MAX_THRESHOLDS 32
+#define UAPS_DETECT_MAX_CANDIDATES 10
+#define UAPS_DETECT_MAX_ROWS 4096
+
+typedef struct uaps_detect_call {
+    uint32_t struct_size;
+    int32_t B, H, W;
+    int32_t num_classes;
+    int32_t class_agnostic;                      /* 1: the class test is skipped and every defect is of class 0 */
+    int32_t T;
+    int32_t max_dets;                            /* 0: no limit */
+    int32_t t1000[UAPS_DETECT_MAX_THRESHOLDS];   /* the first T are read */
+    const int32_t* pred_labels;                  /* [B][H][W] */
+    const int32_t* target_labels;                /* [B][H][W] */
+    const int32_t* pred_count;                   /* [B] */
+    const int32_t* target_count;                 /* [B] */
+    const int64_t* pred_table;                   /* [B][max_pred][9] */
+    const int64_t* target_table;                 /* [B][max_gt][9] */
+    int32_t max_pred, max_gt;
+    const double* scores;                        /* [B][max_pred], or null: sum0 / area */
+    double* score;                               /* [B][max_pred] */
+    int64_t* rank;                               /* [B][max_pred] */
+    int64_t* pred_match;                         /* [B][max_pred][T] */
+    int64_t* pred_inter;                         /* [B][max_pred][T] */
+    int64_t* target_match;                       /* [B][max_gt][T] */
+    int64_t* counts;                             /* [B][num_classes][T + 2] */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_detect_call;
+int uaps_detect_workspace_bytes(int B, int max_pred, int max_gt, int T, size_t* bytes);
+int uaps_detect_match(const uaps_detect_call* call);
+
+/* ---------------------------------------------------------------------------------------------
  * Threshold-sweep histograms: csrc/curves.hip.  Per image and row the histogram of quantised scores split by a binary event -- the one
  * primitive AUROC, average precision, AUPRO, ECE and AURC are formed from (uaps_amd/curves.py does that on the host, in float64).
  * Integers throughout, pro_sum aside (float64, summed in a fixed order): exact, and the same bits from run to run.

@@ -36,6 +36,10 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   match_instances, MatchResult, MATCH_COLUMNS       defect matching against ground truth (two label_instances results): per-defect
                                                     partner / IoU / covered, PQ, SQ, RQ, defect precision / recall, PRO;
                                                     inference.evaluate(..., instances=True)
+  detection_match, DetectionResult, DetectionSums, COCO_THRESHOLDS
+                                                    defect detection scores: COCO's greedy assignment of scored defects at up to 32
+                                                    IoU thresholds (0.1 .. 1.0) at once, exact integers; AP50, AP75, AP@[.50:.95], AR;
+                                                    inference.evaluate(..., detection=True)
   score_curves, plane_curves, CurveResult, CurveSums  threshold-sweep metrics from histograms of quantised scores: pixel AUROC, AP,
                                                     AUPRO, ECE, and AUROC / AURC of the uncertainty map;
                                                     inference.evaluate(..., curves=True)
@@ -97,6 +101,8 @@ from .surface import surface_distances, distance_transform_sq, SurfaceResult, SU
 from . import surface
 from .matching import match_instances, MatchResult, MATCH_COLUMNS
 from . import matching
+from .detection import detection_match, DetectionResult, DetectionSums, COCO_THRESHOLDS
+from . import detection
 from .curves import score_curves, plane_curves, CurveResult, CurveSums
 from . import curves
 from .morphology import morphology          # (the function takes the submodule's name: uaps_amd.morphology(mask, steps, C))

@@ -190,6 +190,8 @@ SIGNATURES = {
     "uaps_surface_distances": (C.c_int, [_PTR]),
     "uaps_match_workspace_bytes": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_size_t)]),
     "uaps_match_instances": (C.c_int, [_PTR]),
+    "uaps_detect_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
+    "uaps_detect_match": (C.c_int, [_PTR]),
     "uaps_curves_workspace_bytes": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_size_t)]),
     "uaps_score_curves": (C.c_int, [_PTR]),
     "uaps_plane_curves": (C.c_int, [_PTR]),
@@ -514,6 +516,20 @@ class MatchCall(C.Structure):
                 ("pred_count", C.c_void_p), ("target_count", C.c_void_p), ("pred_table", C.c_void_p), ("target_table", C.c_void_p),
                 ("max_pred", C.c_int32), ("max_gt", C.c_int32), ("pred_out", C.c_void_p), ("target_out", C.c_void_p),
                 ("counts", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+DETECT_MAX_THRESHOLDS, DETECT_MAX_CANDIDATES, DETECT_MAX_ROWS = 32, 10, 4096     # UAPS_DETECT_MAX_*
+
+
+class DetectCall(C.Structure):
+    """uaps_detect_call (include/uaps_hip.h): every operand of uaps_detect_match, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("num_classes", C.c_int32),
+                ("class_agnostic", C.c_int32), ("T", C.c_int32), ("max_dets", C.c_int32), ("t1000", C.c_int32 * DETECT_MAX_THRESHOLDS),
+                ("pred_labels", C.c_void_p), ("target_labels", C.c_void_p), ("pred_count", C.c_void_p), ("target_count", C.c_void_p),
+                ("pred_table", C.c_void_p), ("target_table", C.c_void_p), ("max_pred", C.c_int32), ("max_gt", C.c_int32),
+                ("scores", C.c_void_p), ("score", C.c_void_p), ("rank", C.c_void_p), ("pred_match", C.c_void_p),
+                ("pred_inter", C.c_void_p), ("target_match", C.c_void_p), ("counts", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
 CURVES_MAX_BINS = 4096                  # UAPS_CURVES_MAX_BINS

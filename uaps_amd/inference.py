@@ -198,7 +198,7 @@ def _one_hot_maps(mask: torch.Tensor, num_classes: int) -> torch.Tensor:
 
 @torch.no_grad()
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None, tiled=None,
-             surface=None, instances=None, curves=None, cleanup=None, components=None) -> Dict[str, float]:
+             surface=None, instances=None, curves=None, cleanup=None, components=None, detection=None) -> Dict[str, float]:
     """The score table of the main head over `batches` of (images, labels): scoring.ConfusionScorer's mIoU, mDice, pixel accuracy
     and "images", then the keys of every family that is switched on, in this order (each scorer of scoring.py documents its own).
     tta=True, or a tuple of scales: the multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main
@@ -208,7 +208,9 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     clear_border / fill_holes), applied to the arg-max mask after the cleanup chain where one is given.  With either, surface= and
     instances= score the cleaned mask and scoring.CleanScorer's two keys are added; every other key is what it is without them.
     surface (scoring.SurfaceScorer), instances (scoring.InstanceScorer): True or a dict of keywords, off for every falsy value.
-    curves (scoring.CurveScorer): True or a dict of keywords -- an empty one asks for the defaults; off for None and False."""
+    curves (scoring.CurveScorer): True or a dict of keywords -- an empty one asks for the defaults; off for None and False.
+    detection (scoring.DetectionScorer): True or a dict of keywords, off for every falsy value; it scores the defects of the masked
+    maps' arg-max like instances=, its keys come last."""
     if cleanup is not None:
         from .morphology import check_steps
         cleanup = check_steps(cleanup)
@@ -220,7 +222,8 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     tiled_kw = _tiled_kwargs(tiled, tta, "evaluate") if tiled else None
     base = scoring.ConfusionScorer()
     scorers = [base, scoring.CleanScorer() if clean else None, scoring.SurfaceScorer(surface) if surface else None,
-               scoring.InstanceScorer(instances) if instances else None, curve]
+               scoring.InstanceScorer(instances) if instances else None, curve,
+               scoring.DetectionScorer(detection) if detection else None]
     scorers = [s for s in scorers if s is not None]
     for x, y in batches:
         f = _forward(model, x, tta, tiled_kw, ("probs",))

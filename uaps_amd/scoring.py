@@ -1,6 +1,6 @@
 """The score families of inference.evaluate, one scorer each.  A scorer is built from its keyword's value (which it checks),
-`update(batch)` scores one batch, and `result(images)` gives its keys in order once the run is over.  Surface, instances and curves sum
-on the device and copy once, in result(); only the confusion matrices are copied per batch."""
+`update(batch)` scores one batch, and `result(images)` gives its keys in order once the run is over.  Surface, instances, curves and
+detection sum on the device and copy once, in result(); only the confusion matrices are copied per batch."""
 from __future__ import annotations
 
 from typing import Dict, NamedTuple, Optional, Tuple
@@ -131,6 +131,43 @@ class InstanceScorer:
                                                     ("DefectRecall(%)", "recall"), ("PRO(%)", "PRO"))}
         out["defects_gt"], out["defects_pred"], out["instance_images_skipped"] = s["n_gt"], s["n_pred"], s["images_skipped"]
         return out
+
+
+class DetectionScorer:
+    """detection=True, or a dict with the keywords iou_thresholds, min_area, connectivity, max_instances, classes and max_dets: the
+    defects of the masked maps' arg-max, each scored by its mean confidence (the largest class probability of the scored maps, after a
+    softmax where they are logits; label_instances(mask, maps=(confidence,))), are assigned to the defects of the labels at every IoU
+    threshold (detection.detection_match; default COCO's 0.50 .. 0.95) -- "mAP(%)" (the mean AP over thresholds and classes, default
+    1 .. C-1), "AP50(%)" and "AP75(%)" (NaN where that threshold is not in the sweep), "DefectAR(%)" (the recall left at the end of the
+    list) and "detection_images_skipped" (images with more defects than max_instances on either side are left out)."""
+    KEYS = ("classes", "connectivity", "iou_thresholds", "max_dets", "max_instances", "min_area")
+
+    def __init__(self, detection):
+        from .detection import COCO_THRESHOLDS, per_mille
+        self.kw = _keywords(detection, self.KEYS, "detection")
+        self.thresholds = tuple(k / 1000.0 for k in per_mille(self.kw.get("iou_thresholds", COCO_THRESHOLDS)))
+        self.parts, self.num_classes = [], 0                 # per batch detection.DetectionSums on the device
+
+    def update(self, batch: Batch) -> None:
+        from .detection import detection_match
+        from .instances import label_instances
+        lab = _label_keywords(self.kw)
+        probs = torch.softmax(batch.scored.float(), dim=1) if batch.from_logits else batch.scored.float()
+        conf = probs.amax(dim=1).contiguous()
+        pred = label_instances(torch.argmax(batch.masked, dim=1), maps=(conf,), **lab)
+        target = label_instances(batch.labels.to(torch.int64), **lab)
+        self.num_classes = batch.masked.shape[1]
+        res = detection_match(pred, target, self.num_classes, iou_thresholds=self.thresholds, max_dets=self.kw.get("max_dets"))
+        self.parts.append(res.sums(self.kw.get("classes")))
+
+    def result(self, images: int) -> Dict:
+        from .detection import summarize
+        classes = self.kw.get("classes")
+        classes = list(range(1, self.num_classes)) if classes is None else [int(c) for c in classes]
+        s = summarize(self.parts, classes, self.thresholds, images)
+        nan = float("nan")
+        return {"mAP(%)": s["mAP"] * 100, "AP50(%)": s.get("AP50", nan) * 100, "AP75(%)": s.get("AP75", nan) * 100,
+                "DefectAR(%)": s["AR"] * 100, "detection_images_skipped": s["images_skipped"]}
 
 
 class CurveScorer:

@@ -148,3 +148,7 @@ def test_c_abi_symbols_and_struct_sizes(tmp_path):
                                      _lib.TTAFoldCall.probs_sum.offset, _lib.TTA_MAX_SCALES]
     # refusals need no device: nothing is launched
     assert L.uaps_tta_views(None) == -1 and L.uaps_tta_fold(None) == -1
+    for fn, call in ((L.uaps_tta_views, _lib.TTAViewsCall()), (L.uaps_tta_fold, _lib.TTAFoldCall())):
+        for size in (0, C.sizeof(call) - 8):                            # a header without `stream`
+            call.struct_size = size
+            assert fn(C.byref(call)) == -1

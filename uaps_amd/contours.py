@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._checks import TOO_BIG as _TOO_BIG
+from ._checks import TOO_BIG as _TOO_BIG, check_instances
 from .instances import InstanceResult
 
 RING_COLUMNS = ("image", "label", "y", "x", "points", "length", "area2")
@@ -212,21 +212,9 @@ def contours(inst: InstanceResult, connectivity: int = 8) -> ContourResult:
     outside [1, max_instances] bound other labels' rings and have none of their own.
     1 <= H, W <= 4096, B*H*W*32 < 2 GiB (a workspace of about 192 bytes a pixel, every array of it below 2 GiB) and a summary below
     2 GiB.  One host read (the totals); an input without a labelled pixel returns empty tensors without a second launch."""
-    if not isinstance(inst, InstanceResult):
-        raise TypeError("contours: an instances.InstanceResult expected")
-    labels = inst.labels
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or labels.dtype != torch.int32:
-        raise TypeError("contours: int32 [B,H,W] labels expected")
+    labels, B, H, W, M = check_instances("contours", inst, MAX_EXTENT)
     if connectivity not in (4, 8):
         raise ValueError("contours: connectivity is 4 or 8")
-    B, H, W = labels.shape
-    M = int(inst.max_instances)
-    if inst.table.dim() != 3 or inst.table.shape[0] != B or inst.table.shape[2] != 9:
-        raise TypeError("contours: the instance table is int64 [B,max_instances,9]")
-    if B < 1 or H < 1 or W < 1 or M < 1:
-        raise ValueError("contours: empty labels")
-    if H > MAX_EXTENT or W > MAX_EXTENT:
-        raise ValueError(f"contours: H and W up to {MAX_EXTENT}")
     if B * H * W * 32 >= _TOO_BIG or B * M * 32 >= _TOO_BIG:
         raise ValueError("contours: B*H*W*32 < 2 GiB and a summary below 2 GiB")
     labels = labels.detach().contiguous()

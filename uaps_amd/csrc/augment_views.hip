@@ -13,10 +13,7 @@
 // the whole program, the CONTRAST pre-pass with the prefix in front of that op.
 // PARITY UNPINNED: cv2 and albumentations are not in the build image; the arithmetic is the one include/uaps_hip.h writes down
 // (tests/augment_views_ref.py restates it stage by stage in numpy), not a measured equality with either library.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-#include "../../include/uaps_hip.h"
+#include "call_common.hpp"
 #include "philox.hpp"
 
 namespace {
@@ -306,9 +303,6 @@ __global__ __launch_bounds__(kThreads) void contrast_final_kernel(Args a, int bl
 }
 
 inline long frame_blocks(int Ho, int Wo) { return ((long)Ho * Wo + kThreads - 1) / kThreads; }
-
-// the first version's struct ends behind `stream`
-constexpr size_t kCallV1 = offsetof(uaps_augment_views_call, stream) + sizeof(uaps_stream_t);
 }  // namespace
 
 extern "C" int uaps_augment_views_workspace_bytes(int V, int B, int Ho, int Wo, size_t* bytes) {
@@ -319,10 +313,8 @@ extern "C" int uaps_augment_views_workspace_bytes(int V, int B, int Ho, int Wo, 
 }
 
 extern "C" int uaps_augment_views(const uaps_augment_views_call* call) {
-    if (!call || call->struct_size < kCallV1 || call->struct_size > sizeof(uaps_augment_views_call)) return UAPS_EINVAL;
-    uaps_augment_views_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, call->struct_size);
+    uaps_augment_views_call c;                  // (this entry point also refuses a struct longer than its own)
+    if (uaps::read_call(call, c) || call->struct_size > sizeof c) return UAPS_EINVAL;
     if (!c.images || !c.rows_host || !c.rows || !c.out || (c.masks != nullptr) != (c.out_mask != nullptr)) return UAPS_EINVAL;
     if ((c.V != 1 && c.V != 2) || (c.Cs != 1 && c.Cs != 3) || c.B <= 0 || c.Hs <= 0 || c.Ws <= 0 || c.Ho <= 0 || c.Wo <= 0) return UAPS_EINVAL;
     if ((long)c.V * c.B > 65535 || (long)c.Ho * c.Wo > 0x7fffffffL || (long)c.Hs * c.Ws > 0x7fffffffL) return UAPS_ERANGE;

@@ -10,13 +10,13 @@
 // Every parent word holds the plane-local index of an earlier or equal pixel of the same component (-1: not foreground), only ever
 // decreases, and a walk ends at the word that names itself: the component's first pixel in raster order.  No workgroup waits for
 // another inside a launch (no flags, no spin loops): every union loop ends by the monotone decrease of the parent words alone.
+//
+// Builds on call_common.hpp alone (kThreads, kWaves of the enclosing namespace): nothing of the loss scaffold comes with this header.
 #pragma once
-#include "loss_common.hpp"
+#include "call_common.hpp"
 
 namespace uaps {
 namespace cc {
-using namespace uaps::loss;
-
 constexpr int kTW = 16, kTH = 16, kTile = kTW * kTH, kPer = kTile / kThreads;   // pixels of a tile per lane
 constexpr unsigned kBorderBit = 0x80000000u;                                    // of an area word (H * W < 2^31 leaves it free)
 constexpr unsigned kAreaMask = 0x7fffffffu;

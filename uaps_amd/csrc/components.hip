@@ -23,7 +23,7 @@
 #include "cc_common.hpp"
 
 namespace {
-using namespace uaps::loss;
+using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::grid_for; using uaps::align256;
 using namespace uaps::cc;
 
 constexpr int kMaxClasses = UAPS_COMP_MAX_CLASSES, kMaxSteps = UAPS_COMP_MAX_STEPS;
@@ -115,7 +115,6 @@ __global__ __launch_bounds__(kThreads) void apply_holes_kernel(ApplyArgs a) {
     }
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int grid_of(long items) { return grid_for(items, kMaxGrid); }
 
 inline int check_dims(int B, int H, int W) {
@@ -129,8 +128,6 @@ inline size_t workspace_for(int B, int H, int W, int planes) {
     const size_t N = (size_t)B * H * W;
     return 2 * align256(4 * N * planes) + align256(8 * N);
 }
-
-constexpr size_t kCompV1 = offsetof(uaps_components_call, stream) + sizeof(uaps_stream_t);
 
 template <typename Args>
 inline void fill_args(Args& a, const uaps_components_call& c, int planes, bool conn8, const long long* in, int* parent, int* area) {
@@ -150,10 +147,8 @@ extern "C" int uaps_components_workspace_bytes(int B, int H, int W, int n_classe
 }
 
 extern "C" int uaps_components(const uaps_components_call* call) {
-    if (!call || call->struct_size < kCompV1) return UAPS_EINVAL;
     uaps_components_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kCompV1);                  // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.mask || !c.out || !c.workspace || c.out == c.mask) return UAPS_EINVAL;
     int rc = check_dims(c.B, c.H, c.W);
     if (rc == UAPS_EINVAL) return rc;
@@ -166,16 +161,12 @@ extern "C" int uaps_components(const uaps_components_call* call) {
         holes = holes || k == UAPS_COMP_FILL_HOLES;
     }
     if (c.n_classes < 1 || c.n_classes > kMaxClasses) return UAPS_EINVAL;
-    for (int k = 0; k < c.n_classes; ++k) {
-        if (c.classes[k] == c.background) return UAPS_EINVAL;
-        for (int j = 0; j < k; ++j)
-            if (c.classes[j] == c.classes[k]) return UAPS_EINVAL;
-    }
+    if (!uaps::distinct_classes(c.classes, c.n_classes, c.background)) return UAPS_EINVAL;
     if (c.connectivity != 4 && c.connectivity != 8) return UAPS_EINVAL;
     if (rc) return rc;
     const int planes = holes ? c.n_classes : 1;
     if (workspace_size(c.B, c.H, c.W, planes) >= kTooBig) return UAPS_ERANGE;
-    if (c.workspace_bytes < workspace_for(c.B, c.H, c.W, planes) || (reinterpret_cast<uintptr_t>(c.workspace) & 255)) return UAPS_EWORKSPACE;
+    if (!uaps::workspace_ok(c.workspace, c.workspace_bytes, workspace_for(c.B, c.H, c.W, planes))) return UAPS_EWORKSPACE;
 
     const long HW = (long)c.H * c.W, N = (long)c.B * HW;
     char* ws = static_cast<char*>(c.workspace);

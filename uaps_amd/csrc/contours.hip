@@ -33,13 +33,10 @@
 //   contour_write_kernel          after the host has read the totals and sized the outputs: points, ring_offsets, rings.
 // Integers only, no float, 4.5 KiB of LDS at the most (the summary's bins; the scans use 64 bytes), no scratch.  The same bits from run to run: every value is a pure
 // function of the labels but the summary's integer sums, whose order does not matter.
-#include <stdint.h>
-#include <string.h>
-#include "loss_common.hpp"
+#include "call_common.hpp"
 
 namespace {
-using namespace uaps::loss;
-typedef unsigned long long u64;
+using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::grid_for; using uaps::align256; using uaps::u64;
 typedef long long i64;
 
 constexpr int kMaxExtent = UAPS_CONTOUR_MAX_EXTENT;
@@ -387,8 +384,6 @@ __global__ __launch_bounds__(kThreads) void contour_write_kernel(ContourArgs A) 
 }
 
 // ---- the host side ------------------------------------------------------------------------------------------------------------------
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct Layout { size_t head, bsum, vbase, ekey, prv0, prv, val0, val1, perm, pslot, csum, bytes; long V1, V, Emax; int nb; };
 
 int lay_out(int B, int H, int W, int M, Layout& L) {
@@ -417,18 +412,14 @@ int lay_out(int B, int H, int W, int M, Layout& L) {
     return UAPS_OK;
 }
 
-constexpr size_t kContourV1 = offsetof(uaps_contour_call, stream) + sizeof(uaps_stream_t);
-
 // the checks both entry points share, and the kernels' arguments
 int prepare(const uaps_contour_call* call, uaps_contour_call& c, ContourArgs& a, Layout& L) {
-    if (!call || call->struct_size < kContourV1) return UAPS_EINVAL;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kContourV1);                       // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.labels || !c.workspace) return UAPS_EINVAL;
     if (c.connectivity != 4 && c.connectivity != 8) return UAPS_EINVAL;
     const int rc = lay_out(c.B, c.H, c.W, c.max_instances, L);
     if (rc) return rc;
-    if (c.workspace_bytes < L.bytes || (reinterpret_cast<uintptr_t>(c.workspace) & 255)) return UAPS_EWORKSPACE;
+    if (!uaps::workspace_ok(c.workspace, c.workspace_bytes, L.bytes)) return UAPS_EWORKSPACE;
     memset(&a, 0, sizeof a);
     char* ws = reinterpret_cast<char*>(c.workspace);
     a.B = c.B; a.H = c.H; a.W = c.W; a.M = c.max_instances; a.conn8 = c.connectivity == 8;

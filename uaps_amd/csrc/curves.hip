@@ -25,11 +25,10 @@
 //   3 pro_kernel             one workgroup per (image, class row): the regions of the class in ascending order, a block scan forms
 //                            the suffix sums of one region, every lane adds suffix / area for its (at most 16) bins in double.  No atomics.
 // Nothing waits inside a launch, no host synchronisation.
-#include <string.h>
-#include "loss_common.hpp"
+#include "loss_common.hpp"               // uaps::pixel: the logits of a pixel group, their softmax and arg-max
 
 namespace {
-using namespace uaps::loss;
+using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::grid_for; using uaps::al16; using uaps::align256;
 
 constexpr int kCT = 512;                  // threads of a curves_kernel workgroup: two waves a SIMD hide each other's wave_add chains
 constexpr int kIter = 2;                  // pixel groups of kCT lanes a workgroup walks
@@ -388,7 +387,6 @@ __global__ __launch_bounds__(kThreads) void pro_kernel(CurveArgs a) {
     if (t == 0) a.n_regions[(long)b * a.K + k] = count;
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline bool dtype_ok(int d) { return d == UAPS_LABEL_U8 || d == UAPS_LABEL_I32 || d == UAPS_LABEL_I64; }
 inline bool finite_f(float v) { return v - v == 0.f; }
 
@@ -451,9 +449,6 @@ inline int check_range(int bins, float lo, float hi, float* inv) {
     if (!finite_f(*inv) || !(*inv > 0.f)) return UAPS_EINVAL;
     return UAPS_OK;
 }
-
-constexpr size_t kCurvesV1 = offsetof(uaps_curves_call, stream) + sizeof(uaps_stream_t);
-constexpr size_t kPlaneV1 = offsetof(uaps_plane_curves_call, stream) + sizeof(uaps_stream_t);
 }  // namespace
 
 extern "C" int uaps_curves_workspace_bytes(int B, int max_regions, int bins, size_t* bytes) {
@@ -465,10 +460,8 @@ extern "C" int uaps_curves_workspace_bytes(int B, int max_regions, int bins, siz
 }
 
 extern "C" int uaps_score_curves(const uaps_curves_call* call) {
-    if (!call || call->struct_size < kCurvesV1) return UAPS_EINVAL;
     uaps_curves_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kCurvesV1);                             // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.scores || !c.target || !c.hist || !c.nan) return UAPS_EINVAL;
     if (c.B <= 0 || c.H <= 0 || c.W <= 0) return UAPS_EINVAL;
     if ((c.from_logits != 0 && c.from_logits != 1) || (c.top_row != 0 && c.top_row != 1)) return UAPS_EINVAL;
@@ -492,7 +485,7 @@ extern "C" int uaps_score_curves(const uaps_curves_call* call) {
     if (regions) {
         if ((double)c.B * c.max_regions * 72.0 >= kTooBig || 4.0 * (double)c.B * c.max_regions * c.bins >= kTooBig) return UAPS_ERANGE;
         need = align256(4 * (size_t)c.B * c.max_regions * c.bins);
-        if (!c.workspace || c.workspace_bytes < need || (reinterpret_cast<uintptr_t>(c.workspace) & 255)) return UAPS_EINVAL;
+        if (!c.workspace || !uaps::workspace_ok(c.workspace, c.workspace_bytes, need)) return UAPS_EINVAL;
     }
 
     CurveArgs a;
@@ -512,10 +505,8 @@ extern "C" int uaps_score_curves(const uaps_curves_call* call) {
 }
 
 extern "C" int uaps_plane_curves(const uaps_plane_curves_call* call) {
-    if (!call || call->struct_size < kPlaneV1) return UAPS_EINVAL;
     uaps_plane_curves_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kPlaneV1);
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.score || !c.pred || !c.target || !c.hist || !c.nan) return UAPS_EINVAL;
     if (c.B <= 0 || c.H <= 0 || c.W <= 0) return UAPS_EINVAL;
     if (c.from_logits != 0) return UAPS_EINVAL;              // a plane is no class probability: nothing to form a softmax over

@@ -21,7 +21,6 @@
 //                         t < npass and takes the first g whose bit in its own taken-mask (LDS, word-major so that the
 //                         lanes hit distinct banks) is clear.  The list is in (IoU descending, g ascending) order and passing is monotone
 //                         along it, so this is the literal greedy rule.  tp is carried in a register and stored at a class change.
-#include <string.h>
 #include "pair_count.hpp"
 
 namespace {
@@ -31,7 +30,7 @@ constexpr int kMaxRows = UAPS_DETECT_MAX_ROWS;
 constexpr int kOrderThreads = 1024;
 constexpr int kPer = kMaxRows / kOrderThreads;      // table rows a thread of order_kernel holds
 constexpr int kScan = 4;                            // row words a lane of candidates_kernel reads before it tests
-typedef unsigned long long u64;
+using uaps::u64;
 
 struct DetArgs {
     MatchArgs m;                                    // B, Mp, Mg, C, agnostic, counts, tables and the pair matrix
@@ -306,8 +305,6 @@ inline int check_sizes(int B, int Mp, int Mg, int T) {
     if (T < 1 || T > kMaxT || Mp > kMaxRows || Mg > kMaxRows) return UAPS_ERANGE;
     return rc;
 }
-
-constexpr size_t kDetectV1 = offsetof(uaps_detect_call, stream) + sizeof(uaps_stream_t);
 }  // namespace
 
 extern "C" int uaps_detect_workspace_bytes(int B, int max_pred, int max_gt, int T, size_t* bytes) {
@@ -319,10 +316,8 @@ extern "C" int uaps_detect_workspace_bytes(int B, int max_pred, int max_gt, int 
 }
 
 extern "C" int uaps_detect_match(const uaps_detect_call* call) {
-    if (!call || call->struct_size < kDetectV1) return UAPS_EINVAL;
     uaps_detect_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kDetectV1);                    // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.pred_labels || !c.target_labels || !c.pred_count || !c.target_count || !c.pred_table || !c.target_table) return UAPS_EINVAL;
     if (!c.score || !c.rank || !c.pred_match || !c.pred_inter || !c.target_match || !c.counts || !c.workspace) return UAPS_EINVAL;
     if (c.H <= 0 || c.W <= 0 || c.max_dets < 0) return UAPS_EINVAL;
@@ -335,7 +330,7 @@ extern "C" int uaps_detect_match(const uaps_detect_call* call) {
     for (int t = 0; t < c.T; ++t)
         if (c.t1000[t] < 100 || c.t1000[t] > 1000 || (t > 0 && c.t1000[t] <= c.t1000[t - 1])) return UAPS_ERANGE;
     const Layout l = layout(c.B, c.max_pred, c.max_gt);
-    if (c.workspace_bytes < l.total || (reinterpret_cast<uintptr_t>(c.workspace) & 255)) return UAPS_EINVAL;
+    if (!uaps::workspace_ok(c.workspace, c.workspace_bytes, l.total)) return UAPS_EINVAL;
 
     DetArgs d;
     memset(&d, 0, sizeof d);

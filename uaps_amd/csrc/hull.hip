@@ -28,12 +28,10 @@
 //                         vertices gives the largest c and the range of d(p) = ex (px - vx) + ey (py - vy)); the two
 //                         minimisations compare fractions by cross-multiplication in 128-bit integers, ties to the lowest edge.
 // No float, no host synchronisation, no scratch; LDS 8 (H + 1) bytes + 128.
-#include <stdint.h>
-#include <string.h>
 #include "cc_common.hpp"
 
 namespace {
-using namespace uaps::loss;
+using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::grid_for; using uaps::align256; using uaps::u64;
 using uaps::cc::run_end;
 
 constexpr int kCols = UAPS_HULL_COLUMNS;
@@ -43,7 +41,6 @@ constexpr int kItems = 2;                                       // items a wave
 constexpr int kMaxGrid = 1 << 16;
 constexpr unsigned kAbsent = 0xffffffffu;
 constexpr int kNoEdge = 0x7fffffff;
-typedef unsigned long long u64;
 typedef unsigned __int128 u128;
 
 struct HullArgs {
@@ -313,10 +310,6 @@ __global__ __launch_bounds__(kThreads) void hull_measure_kernel(HullArgs a) {
         out[10] = r_y; out[11] = r_x; out[12] = r_ey; out[13] = r_ex; out[14] = r_dmin; out[15] = r_dmax; out[16] = r_c;
     }
 }
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-constexpr size_t kHullV1 = offsetof(uaps_hull_call, stream) + sizeof(uaps_stream_t);
 }  // namespace
 
 extern "C" int uaps_hull_workspace_bytes(int B, int H, int W, int max_instances, size_t* bytes) {
@@ -329,17 +322,15 @@ extern "C" int uaps_hull_workspace_bytes(int B, int H, int W, int max_instances,
 }
 
 extern "C" int uaps_hull_descriptors(const uaps_hull_call* call) {
-    if (!call || call->struct_size < kHullV1) return UAPS_EINVAL;
     uaps_hull_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kHullV1);                  // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.labels || !c.table || !c.workspace || (const void*)c.table == (const void*)c.labels) return UAPS_EINVAL;
     if (c.B <= 0 || c.H <= 0 || c.W <= 0 || c.max_instances < 1) return UAPS_EINVAL;
     size_t need = 0;
     const int rc = uaps_hull_workspace_bytes(c.B, c.H, c.W, c.max_instances, &need);
     if (rc) return rc;
     if ((double)c.B * c.max_instances * (8.0 * kCols) >= kTooBig) return UAPS_ERANGE;
-    if (c.workspace_bytes < need || (reinterpret_cast<uintptr_t>(c.workspace) & 255)) return UAPS_EWORKSPACE;
+    if (!uaps::workspace_ok(c.workspace, c.workspace_bytes, need)) return UAPS_EWORKSPACE;
 
     hipStream_t st = (hipStream_t)c.stream;
     const long defects = (long)c.B * c.max_instances;           // < 2^28 / 17

@@ -36,7 +36,7 @@
 #include "cc_common.hpp"
 
 namespace {
-using namespace uaps::loss;
+using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::grid_for; using uaps::align256;
 using namespace uaps::cc;                  // the union-find and the three labelling passes, shared with components.hip
 
 constexpr int kChunk = kThreads;                                                // raster chunk of the numbering scan
@@ -229,7 +229,6 @@ __global__ __launch_bounds__(kThreads) void final_kernel(FinalArgs a) {
     if (pend_k > 0 && lane == 0) flush_row(a, pend_b, pend_k, pend);
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline long chunks_of(long HW) { return (HW + kChunk - 1) / kChunk; }
 inline int grid_of(long items) { return grid_for(items, kMaxGrid); }
 
@@ -243,8 +242,6 @@ inline size_t workspace_for(int B, int H, int W) {
     const size_t N = (size_t)B * H * W;
     return 2 * align256(4 * N) + align256(4 * (size_t)B * chunks_of((long)H * W));
 }
-
-constexpr size_t kInstV1 = offsetof(uaps_instances_call, stream) + sizeof(uaps_stream_t);
 
 // ---------------------------------------------------------------------------------------------- run-length masks
 constexpr int kRleMax = UAPS_RLE_MAX_CLASSES;
@@ -338,13 +335,9 @@ __global__ __launch_bounds__(kThreads) void rle_decode_kernel(DecodeArgs a) {
     }
 }
 
-constexpr size_t kRleV1 = offsetof(uaps_rle_call, stream) + sizeof(uaps_stream_t);
-
 // the checks the three entry points share; 0 or the code.  `c` receives the caller's struct, size-versioned.
 inline int read_rle(const uaps_rle_call* call, uaps_rle_call& c) {
-    if (!call || call->struct_size < kRleV1) return UAPS_EINVAL;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kRleV1);
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (c.B <= 0 || c.H <= 0 || c.W <= 0) return UAPS_EINVAL;
     if (c.n_classes < 1 || c.n_classes > kRleMax) return UAPS_ERANGE;
     if ((double)c.H * c.W >= kTooBig || (double)c.B * c.H * c.W * 8.0 >= kTooBig) return UAPS_ERANGE;
@@ -370,10 +363,8 @@ extern "C" int uaps_instances_workspace_bytes(int B, int H, int W, size_t* bytes
 }
 
 extern "C" int uaps_label_instances(const uaps_instances_call* call) {
-    if (!call || call->struct_size < kInstV1) return UAPS_EINVAL;
     uaps_instances_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kInstV1);                  // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.mask || !c.labels || !c.count || !c.table || !c.workspace) return UAPS_EINVAL;
     if (c.map1 && !c.map0) return UAPS_EINVAL;
     if ((c.connectivity != 4 && c.connectivity != 8) || c.min_area < 1 || c.max_instances < 1) return UAPS_EINVAL;

@@ -1,39 +1,30 @@
 // What the fused loss files (loss_seg, loss_cps, loss_ucc, loss_binary, loss_cct_dct, loss_mean_teacher, pair_ops) share; each keeps
 // only its column layout, per-pixel arithmetic, finalize formulas and entry points.
-//   uaps::loss    the launch scaffold (block size, grid rule, the 2 GiB refusal, the alignment rule of the four-pixel form, the
-//                 dispatch on C and on V) and the reduction: wave shuffles, one LDS round over the block's four waves added as
-//                 (r0 + r1) + (r2 + r3), one partial row per block, column sums in double in block order.  That fixed order is what
-//                 makes two runs give the same bits: it lives here and nowhere else.
+//   uaps::loss    the reduction: wave shuffles, one LDS round over the block's four waves added as (r0 + r1) + (r2 + r3), one
+//                 partial row per block, column sums in double in block order.  That fixed order is what makes two runs give the
+//                 same bits: it lives here and nowhere else.  The dispatch on C and on V.  The rest of the launch scaffold (block
+//                 size, grid rule, the 2 GiB refusal, the alignment rule of the four-pixel form) is call_common.hpp's, re-exported
+//                 here.
 //   uaps::pixel   per-pixel device helpers: a lane holds all C class logits of V consecutive pixels (V = 4: one float4 per class
 //                 plane, V = 1 otherwise) in registers.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <math.h>
-#include "../../include/uaps_hip.h"
-#include "hints.hpp"
+#include "call_common.hpp"
 
 namespace uaps {
 namespace loss {
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr double kTooBig = 2147483648.0;       // bytes: every tensor an entry point takes stays below 2 GiB
-
-// one block per kThreads items, at least one and at most `cap` (the lanes stride over the rest)
-inline int grid_for(long items, int cap) { const long g = (items + kThreads - 1) / kThreads; return (int)(g > cap ? cap : (g < 1 ? 1 : g)); }
-// the four-pixel form needs 16-byte aligned float / int64 pointers and 4-byte aligned pseudo-label bytes
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+// the launch scaffold is call_common.hpp's, shared with every other entry point; the loss files go on finding it here
+using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::grid_for; using uaps::al16; using uaps::al4;
 
 // return CALL(C) for the class counts the kernels are built for
 #define UAPS_BY_C(C, CALL) \
     switch (C) { case 2: return CALL(2); case 3: return CALL(3); case 4: return CALL(4); case 5: return CALL(5); \
                  case 6: return CALL(6); case 7: return CALL(7); case 8: return CALL(8); default: return UAPS_ERANGE; }
 // KERNEL<C, 4> when `vec` (four pixels a lane), else KERNEL<C, 1>: the same grid, kThreads threads, the same arguments
-#define UAPS_LAUNCH_V(vec, KERNEL, C, grid, stream, ...)                                                        \
-    do {                                                                                                        \
-        if (vec) UAPS_LAUNCH_MAIN((KERNEL<C, 4>), dim3(grid), dim3(uaps::loss::kThreads), 0, stream, __VA_ARGS__); \
-        else UAPS_LAUNCH_MAIN((KERNEL<C, 1>), dim3(grid), dim3(uaps::loss::kThreads), 0, stream, __VA_ARGS__);  \
+#define UAPS_LAUNCH_V(vec, KERNEL, C, grid, stream, ...)                                                  \
+    do {                                                                                                  \
+        if (vec) UAPS_LAUNCH_MAIN((KERNEL<C, 4>), dim3(grid), dim3(uaps::kThreads), 0, stream, __VA_ARGS__); \
+        else UAPS_LAUNCH_MAIN((KERNEL<C, 1>), dim3(grid), dim3(uaps::kThreads), 0, stream, __VA_ARGS__);  \
     } while (0)
 
 __device__ __forceinline__ float wave_sum(float v) {

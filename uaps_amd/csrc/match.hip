@@ -13,7 +13,6 @@
 // Both reductions run the match test on their own partner ((double) inter > threshold * (double) union); at thresholds >= 0.5 a match
 // is unique and is the component's largest intersection, so the two sides agree.  n_pred, n_gt and tp reach `counts` by 64-bit integer
 // atomicAdd.
-#include <string.h>
 #include "pair_count.hpp"
 
 namespace {
@@ -121,8 +120,6 @@ __global__ __launch_bounds__(kThreads) void reduce_target_kernel(MatchArgs a) {
         if (m) atomicAdd(row, 1ull);
     }
 }
-
-constexpr size_t kMatchV1 = offsetof(uaps_match_call, stream) + sizeof(uaps_stream_t);
 }  // namespace
 
 extern "C" int uaps_match_workspace_bytes(int B, int max_pred, int max_gt, size_t* bytes) {
@@ -134,10 +131,8 @@ extern "C" int uaps_match_workspace_bytes(int B, int max_pred, int max_gt, size_
 }
 
 extern "C" int uaps_match_instances(const uaps_match_call* call) {
-    if (!call || call->struct_size < kMatchV1) return UAPS_EINVAL;
     uaps_match_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kMatchV1);                     // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.pred_labels || !c.target_labels || !c.pred_count || !c.target_count || !c.pred_table || !c.target_table) return UAPS_EINVAL;
     if (!c.pred_out || !c.target_out || !c.counts || !c.workspace) return UAPS_EINVAL;
     if (c.H <= 0 || c.W <= 0) return UAPS_EINVAL;
@@ -149,7 +144,7 @@ extern "C" int uaps_match_instances(const uaps_match_call* call) {
     if (!(c.iou_threshold >= 0.5 && c.iou_threshold < 1.0)) return UAPS_ERANGE;
     if (rc) return rc;
     const size_t need = align256(4 * (size_t)c.B * c.max_pred * c.max_gt);
-    if (c.workspace_bytes < need || (reinterpret_cast<uintptr_t>(c.workspace) & 255)) return UAPS_EINVAL;
+    if (!uaps::workspace_ok(c.workspace, c.workspace_bytes, need)) return UAPS_EINVAL;
 
     MatchArgs a;
     a.B = c.B; a.Mp = c.max_pred; a.Mg = c.max_gt; a.C = c.num_classes; a.agnostic = c.class_agnostic;

@@ -20,13 +20,10 @@
 //               every visited result is struck from F.
 // The A / T result planes exist for G classes at a time (G = all of them wherever that fits): n + 2 + 2G planes of R x sw words, at
 // most 64 KiB.  No atomics, no scratch, integer work only; a pixel's result does not depend on the tiling.
-#include <string.h>
-#include <stddef.h>
-#include "loss_common.hpp"
+#include "call_common.hpp"
 
 namespace {
-using namespace uaps::loss;
-using u64 = unsigned long long;
+using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::u64;
 
 constexpr int kMaxSteps = 8, kMaxSel = 8, kMaxRadius = 15, kMaxReach = 64, kMaxExtent = 4096;
 constexpr int kLdsWords = 64 * 1024 / 8;       // the plane budget of a workgroup, in 64-bit words
@@ -267,8 +264,6 @@ int make_plan(int H, int W, int n, int reach, int forced, Plan& p) {
     }
     return UAPS_ERANGE;
 }
-
-constexpr size_t kMorphV1 = offsetof(uaps_morph_call, stream) + sizeof(uaps_stream_t);
 }  // namespace
 
 extern "C" int uaps_morph_band_rows(int H, int W, int n_planes, int reach, int* rows) {
@@ -282,21 +277,15 @@ extern "C" int uaps_morph_band_rows(int H, int W, int n_planes, int reach, int* 
 }
 
 extern "C" int uaps_morphology(const uaps_morph_call* call) {
-    if (!call || call->struct_size < kMorphV1) return UAPS_EINVAL;
     uaps_morph_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kMorphV1);                 // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.mask || !c.out || (const void*)c.out == (const void*)c.mask) return UAPS_EINVAL;
     if (c.B <= 0 || c.H <= 0 || c.W <= 0) return UAPS_EINVAL;
     if (c.n_steps < 1 || c.n_steps > kMaxSteps || c.n_classes < 1 || c.n_classes > kMaxSel || c.band_rows < 0) return UAPS_EINVAL;
     for (int s = 0; s < c.n_steps; ++s)
         if (c.op[s] < UAPS_MORPH_ERODE || c.op[s] > UAPS_MORPH_BOUNDARY || c.footprint[s] < UAPS_MORPH_SQUARE || c.footprint[s] > UAPS_MORPH_DISK)
             return UAPS_EINVAL;
-    for (int k = 0; k < c.n_classes; ++k) {
-        if (c.classes[k] == c.background) return UAPS_EINVAL;
-        for (int j = 0; j < k; ++j)
-            if (c.classes[j] == c.classes[k]) return UAPS_EINVAL;
-    }
+    if (!uaps::distinct_classes(c.classes, c.n_classes, c.background)) return UAPS_EINVAL;
     int reach = 0;
     for (int s = 0; s < c.n_steps; ++s) {
         if (c.radius[s] < 1 || c.radius[s] > kMaxRadius) return UAPS_ERANGE;

@@ -15,11 +15,12 @@
 //                        The sending lane does the class test: two table reads per run, not per pixel, and all of a lane's reads
 //                        of one round before its adds.
 // The kernels have internal linkage: every file that includes this header carries its own copy.
+// Builds on call_common.hpp alone and names what it takes from it: nothing of the loss scaffold comes with this header.
 #pragma once
-#include "loss_common.hpp"
+#include "call_common.hpp"
 
 namespace {
-using namespace uaps::loss;
+using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::grid_for; using uaps::al16; using uaps::align256;
 
 constexpr int kSpan = 4;                  // groups of 64 lanes a wave walks in pair_count_kernel
 
@@ -184,8 +185,6 @@ __global__ __launch_bounds__(kThreads) void pair_count_kernel(MatchArgs a) {
         }
     }
 }
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // the rules of the pair matrix: 0 or the code
 inline int check_matrix(int B, int Mp, int Mg) {

@@ -21,13 +21,11 @@
 //            first lanes send them directly.  atomicAdd, and atomicMax for pmax, on non-negative integers: two runs and both
 //            forms give the same bits.
 // No workspace, no float, no host synchronisation, no scratch.
-#include <stdint.h>
-#include <string.h>
 #include "cc_common.hpp"
 #include "table_flush.hpp"
 
 namespace {
-using namespace uaps::loss;
+using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::grid_for; using uaps::u64;
 using uaps::cc::run_end;
 using uaps::table::table_lds_zero;
 using uaps::table::table_lds_flush;
@@ -38,7 +36,6 @@ constexpr int kItems = 2;                               // items a wave
 constexpr int kLdsRows = uaps::table::kLdsRows;
 constexpr int kMaxGrid = uaps::table::kMaxGrid;
 constexpr int kMaxCol = 9;                              // pmax: the table's one maximum column (table_flush.hpp)
-typedef unsigned long long u64;
 
 struct ShapeArgs {
     int H, W, M, nchunks, bpi;                          // bpi: workgroups an image
@@ -169,15 +166,11 @@ __global__ __launch_bounds__(kThreads) void shape_accumulate_kernel(ShapeArgs a)
     }
     if (LDS) table_lds_flush<kCols, kMaxCol>(acc, out, words);
 }
-
-constexpr size_t kShapeV1 = offsetof(uaps_shape_call, stream) + sizeof(uaps_stream_t);
 }  // namespace
 
 extern "C" int uaps_shape_descriptors(const uaps_shape_call* call) {
-    if (!call || call->struct_size < kShapeV1) return UAPS_EINVAL;
     uaps_shape_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kShapeV1);                 // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.labels || !c.table || (const void*)c.table == (const void*)c.labels) return UAPS_EINVAL;
     if (c.B <= 0 || c.H <= 0 || c.W <= 0 || c.max_instances < 1) return UAPS_EINVAL;
     if (c.H > UAPS_SHAPE_MAX_EXTENT || c.W > UAPS_SHAPE_MAX_EXTENT) return UAPS_ERANGE;

@@ -23,13 +23,10 @@
 // the `points` column of the summary copy.  simplify_sum / _base / _apply scan the kept counts into the new ring offsets, and
 // simplify_write_kernel, after the host has read the total, stores every kept point at its ring's base plus its rank.
 // Integers only, no float, no scratch; only integer max / min / add atomics, so every form and every run gives the same bits.
-#include <stdint.h>
-#include <string.h>
-#include "loss_common.hpp"
+#include "call_common.hpp"
 
 namespace {
-using namespace uaps::loss;
-typedef unsigned long long u64;
+using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::grid_for; using uaps::align256; using uaps::u64;
 typedef long long i64;
 
 constexpr int kWaveCap = UAPS_SIMPLIFY_WAVE_MAX, kLdsCap = UAPS_SIMPLIFY_LDS_MAX;
@@ -462,8 +459,6 @@ __global__ __launch_bounds__(kThreads) void simplify_write_kernel(SimplifyArgs A
 }
 
 // ---- the host side ------------------------------------------------------------------------------------------------------------------
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 struct Layout { size_t head, bsum, kept, area, noff, list0, list1, pring, slot, glo, ghi, gmax, gidx, bytes; int nb; };
 
 int lay_out(i64 n_points, i64 n_rings, Layout& L) {
@@ -489,20 +484,16 @@ int lay_out(i64 n_points, i64 n_rings, Layout& L) {
     return UAPS_OK;
 }
 
-constexpr size_t kSimplifyV1 = offsetof(uaps_simplify_call, stream) + sizeof(uaps_stream_t);
-
 // the checks both entry points share, and the kernels' arguments
 int prepare(const uaps_simplify_call* call, uaps_simplify_call& c, SimplifyArgs& a, Layout& L) {
-    if (!call || call->struct_size < kSimplifyV1) return UAPS_EINVAL;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kSimplifyV1);                      // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.points || !c.ring_offsets || !c.rings || !c.workspace) return UAPS_EINVAL;
     if (c.B < 1 || c.max_instances < 1 || c.e16 < 0 || c.e16 > kMaxE16) return UAPS_EINVAL;
     if (c.wave_max > kWaveCap || c.lds_max > kLdsCap || c.wave_max < UAPS_SIMPLIFY_OFF || c.lds_max < UAPS_SIMPLIFY_OFF) return UAPS_EINVAL;
     if ((double)c.B * c.max_instances * 32.0 >= kTooBig) return UAPS_ERANGE;
     const int rc = lay_out(c.n_points, c.n_rings, L);
     if (rc) return rc;
-    if (c.workspace_bytes < L.bytes || (reinterpret_cast<uintptr_t>(c.workspace) & 255)) return UAPS_EWORKSPACE;
+    if (!uaps::workspace_ok(c.workspace, c.workspace_bytes, L.bytes)) return UAPS_EWORKSPACE;
     memset(&a, 0, sizeof a);
     char* ws = reinterpret_cast<char*>(c.workspace);
     a.N = (long)c.n_points; a.L = (long)c.n_rings; a.rows = (long)c.B * c.max_instances; a.M = c.max_instances;

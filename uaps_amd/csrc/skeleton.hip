@@ -27,18 +27,14 @@
 //   SE); the five counts travel as one packed word (12 bits each: a group adds at most 128 to a field) and are reduced over runs of
 //   equal labels (cc_common.hpp's run_end); the flush is table_flush.hpp's, shared with shapes.hip.
 // Integers only, no float, no scratch, no host synchronisation.
-#include <stdint.h>
-#include <string.h>
-#include <stddef.h>
 #include "cc_common.hpp"
 #include "table_flush.hpp"
 
 namespace {
-using namespace uaps::loss;
+using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::grid_for; using uaps::align256; using uaps::u64;
 using uaps::cc::run_end;
 using uaps::table::table_lds_zero;
 using uaps::table::table_lds_flush;
-typedef unsigned long long u64;
 
 constexpr int kMaxSel = UAPS_SKEL_MAX_CLASSES, kMaxExtent = UAPS_SKEL_MAX_EXTENT, kMaxS = UAPS_SKEL_MAX_SUB_ITERS;
 constexpr int kLdsWords = 64 * 1024 / 8;        // the budget of a workgroup, in 64-bit words
@@ -233,9 +229,6 @@ int make_plan(int H, int W, int S, int forced, Plan& p) {
 }
 
 size_t plane_bytes(int B, int H, int W, int n) { return (size_t)n * B * H * ((W + 63) / 64) * 8; }
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-constexpr size_t kSkelV1 = offsetof(uaps_skeleton_call, stream) + sizeof(uaps_stream_t);
 }  // namespace
 
 extern "C" int uaps_skeleton_workspace_bytes(int B, int H, int W, int n_classes, size_t* bytes) {
@@ -259,20 +252,14 @@ extern "C" int uaps_skeleton_band_rows(int H, int W, int n_planes, int S, int* r
 }
 
 extern "C" int uaps_skeletonize(const uaps_skeleton_call* call) {
-    if (!call || call->struct_size < kSkelV1) return UAPS_EINVAL;
     uaps_skeleton_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kSkelV1);                  // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.mask || !c.out || !c.converged || !c.workspace || (const void*)c.out == (const void*)c.mask) return UAPS_EINVAL;
     if (c.B <= 0 || c.H <= 0 || c.W <= 0) return UAPS_EINVAL;
     if (c.n_classes < 1 || c.n_classes > kMaxSel || c.band_rows < 0) return UAPS_EINVAL;
     if (c.max_iters < 1 || c.max_iters > UAPS_SKEL_MAX_ITERS) return UAPS_EINVAL;
     if (c.sub_iters != 0 && (c.sub_iters < 2 || c.sub_iters > kMaxS || (c.sub_iters & 1))) return UAPS_EINVAL;
-    for (int k = 0; k < c.n_classes; ++k) {
-        if (c.classes[k] == c.background) return UAPS_EINVAL;
-        for (int j = 0; j < k; ++j)
-            if (c.classes[j] == c.classes[k]) return UAPS_EINVAL;
-    }
+    if (!uaps::distinct_classes(c.classes, c.n_classes, c.background)) return UAPS_EINVAL;
     size_t need = 0;
     int rc = uaps_skeleton_workspace_bytes(c.B, c.H, c.W, c.n_classes, &need);
     if (rc) return rc;
@@ -280,7 +267,7 @@ extern "C" int uaps_skeletonize(const uaps_skeleton_call* call) {
     Plan p;
     rc = make_plan(c.H, c.W, S, c.band_rows, p);
     if (rc) return rc;
-    if (c.workspace_bytes < need || (reinterpret_cast<uintptr_t>(c.workspace) & 255)) return UAPS_EWORKSPACE;
+    if (!uaps::workspace_ok(c.workspace, c.workspace_bytes, need)) return UAPS_EWORKSPACE;
 
     SkelArgs a;
     memset(&a, 0, sizeof a);
@@ -448,15 +435,11 @@ __global__ __launch_bounds__(kThreads) void skeleton_stats_kernel(StatArgs a) {
     }
     if (LDS) table_lds_flush<kCols, kMaxCol>(acc, out, words);
 }
-
-constexpr size_t kStatsV1 = offsetof(uaps_skeleton_stats_call, stream) + sizeof(uaps_stream_t);
 }  // namespace
 
 extern "C" int uaps_skeleton_stats(const uaps_skeleton_stats_call* call) {
-    if (!call || call->struct_size < kStatsV1) return UAPS_EINVAL;
     uaps_skeleton_stats_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kStatsV1);                 // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.labels || !c.skel || !c.table) return UAPS_EINVAL;
     if ((const void*)c.table == (const void*)c.labels || (const void*)c.table == (const void*)c.skel) return UAPS_EINVAL;
     if (c.B <= 0 || c.H <= 0 || c.W <= 0 || c.max_instances < 1 || c.n_classes < 1 || c.n_classes > kMaxSel) return UAPS_EINVAL;

@@ -18,11 +18,10 @@
 //                  workgroup histograms kChunk values in LDS (a wave whose lanes all hit one bin sends one add) and flushes the
 //                  bins it touched with integer atomics; one workgroup per pair then finds each rank's bin with a block scan.
 // No launch waits for another workgroup; launch boundaries are the only coherence points.
-#include <string.h>
-#include "loss_common.hpp"
+#include "call_common.hpp"
 
 namespace {
-using namespace uaps::loss;
+using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::grid_for; using uaps::align256;
 
 constexpr int kExtent = UAPS_SURFACE_MAX_EXTENT;
 constexpr int kCols = UAPS_SURFACE_COLUMNS;
@@ -431,7 +430,6 @@ __global__ __launch_bounds__(kThreads) void argmax_kernel(const float* __restric
     }
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline bool dtype_ok(int d) { return d == UAPS_LABEL_U8 || d == UAPS_LABEL_I32 || d == UAPS_LABEL_I64; }
 
 inline int check_extent(int B, int H, int W) {
@@ -475,9 +473,6 @@ void launch_col(const ColArgs& a, hipStream_t st) {
     const long groups = (long)a.B * 2 * ((a.W + 63) / 64);
     hipLaunchKernelGGL((col_kernel<C, false>), dim3((unsigned)groups), dim3(a.nseg * 64), 0, st, a);
 }
-
-constexpr size_t kEdtV1 = offsetof(uaps_edt_call, stream) + sizeof(uaps_stream_t);
-constexpr size_t kSurfV1 = offsetof(uaps_surface_call, stream) + sizeof(uaps_stream_t);
 }  // namespace
 
 extern "C" int uaps_edt_workspace_bytes(int B, int H, int W, size_t* bytes) {
@@ -489,10 +484,8 @@ extern "C" int uaps_edt_workspace_bytes(int B, int H, int W, size_t* bytes) {
 }
 
 extern "C" int uaps_edt_sq(const uaps_edt_call* call) {
-    if (!call || call->struct_size < kEdtV1) return UAPS_EINVAL;
     uaps_edt_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kEdtV1);                   // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.mask || !c.out || !c.workspace || !dtype_ok(c.mask_dtype)) return UAPS_EINVAL;
     const int rc = check_edt(c.B, c.H, c.W);
     if (rc) return rc;
@@ -516,10 +509,8 @@ extern "C" int uaps_surface_workspace_bytes(int B, int C, int H, int W, size_t* 
 }
 
 extern "C" int uaps_surface_distances(const uaps_surface_call* call) {
-    if (!call || call->struct_size < kSurfV1) return UAPS_EINVAL;
     uaps_surface_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kSurfV1);
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.target || !c.table || !c.workspace) return UAPS_EINVAL;
     if ((c.pred != nullptr) == (c.pred_scores != nullptr)) return UAPS_EINVAL;
     if (!dtype_ok(c.target_dtype) || (c.pred && !dtype_ok(c.pred_dtype))) return UAPS_EINVAL;

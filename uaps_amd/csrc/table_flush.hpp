@@ -5,14 +5,12 @@
 //                       lanes add into it, and table_lds_flush sends the non-zero words to the table with 64-bit atomics
 //   direct form         above kLdsRows rows the first lanes send to the table themselves
 // atomicAdd, and atomicMax for the maximum column, on non-negative integers only: two runs and both forms give the same bits.
+// Builds on call_common.hpp alone (kThreads, u64 of the enclosing namespace): nothing of the loss scaffold comes with this header.
 #pragma once
-#include "loss_common.hpp"
+#include "call_common.hpp"
 
 namespace uaps {
 namespace table {
-using namespace uaps::loss;
-typedef unsigned long long u64;
-
 constexpr int kLdsRows = UAPS_SHAPE_LDS_ROWS;
 constexpr int kMaxGrid = 1 << 24;
 

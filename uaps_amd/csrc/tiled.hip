@@ -12,12 +12,11 @@
 // cnt = ceil((n - t) / s) + 1 and last = n - t; tile i starts at i * s for i < cnt - 1 and at `last` for i = cnt - 1.  Pixel p lies in
 // the regular tiles k - 1 and k, k = p / s (where those exist and reach p: t <= 2 s, so k - 2 never does), and in the last tile when
 // p >= last: three candidates, already in ascending order.
-#include <string.h>
-#include "loss_common.hpp"
+#include "loss_common.hpp"               // uaps::pixel (the softmax of a pixel's logits), UAPS_BY_C, UAPS_LAUNCH_V
 #include "rn_math.hpp"
 
 namespace {
-using namespace uaps::loss;
+using uaps::kThreads; using uaps::kTooBig; using uaps::grid_for; using uaps::al16;
 constexpr int kMaxChunks = UAPS_TILE_MAX_CHUNKS, kMaxMaps = UAPS_TILE_MAX_MAPS;
 constexpr int kMaxBlocks = 1 << 20;      // every tensor is below 2 GiB: a grid never needs more; the lanes stride over the rest anyway
 
@@ -183,10 +182,6 @@ __global__ __launch_bounds__(kThreads, 2) void tile_fold_kernel(FoldArgs a) {
 
 inline bool too_big(double elems, double bytes_each) { return elems * bytes_each >= kTooBig; }
 
-// the first version's structs end behind `stream`
-constexpr size_t kCutV1 = offsetof(uaps_tile_cut_call, stream) + sizeof(uaps_stream_t);
-constexpr size_t kFoldV1 = offsetof(uaps_tile_fold_call, stream) + sizeof(uaps_stream_t);
-
 template <int C>
 int launch_fold(const FoldArgs& a, bool vec, hipStream_t st) {
     const long groups = (long)a.B * a.H * a.W / (vec ? 4 : 1);
@@ -214,10 +209,8 @@ extern "C" int uaps_tile_origins(int n, int tile, int overlap, int* count, int* 
 }
 
 extern "C" int uaps_tile_cut(const uaps_tile_cut_call* call) {
-    if (!call || call->struct_size < kCutV1) return UAPS_EINVAL;
     uaps_tile_cut_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kCutV1);                // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.x || !c.out || c.B <= 0 || c.Cin <= 0) return UAPS_EINVAL;
     if (const int rc = check_geometry(c.H, c.W, c.th, c.tw, c.oy, c.ox)) return rc;
     if (too_big((double)c.B * c.Cin * c.H * c.W, 4.0)) return UAPS_ERANGE;
@@ -236,10 +229,8 @@ extern "C" int uaps_tile_cut(const uaps_tile_cut_call* call) {
 }
 
 extern "C" int uaps_tile_fold(const uaps_tile_fold_call* call) {
-    if (!call || call->struct_size < kFoldV1) return UAPS_EINVAL;
     uaps_tile_fold_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kFoldV1);
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.wy || !c.wx || c.B <= 0 || c.C < 0 || c.n_maps < 0 || c.n_chunks <= 0 || c.tiles_per_chunk <= 0) return UAPS_EINVAL;
     const bool any_class_out = c.probs || c.mask || c.conf;
     if ((c.C == 0 && any_class_out) || (!any_class_out && c.n_maps == 0) || (c.C > 0 && !any_class_out)) return UAPS_EINVAL;

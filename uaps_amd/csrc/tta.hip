@@ -12,12 +12,11 @@
 // value = l0h * (l0w * v00 + l1w * v01) + l1h * (l0w * v10 + l1w * v11).  src is rounded on its own (mul_rn): fused into l1 it would
 // be a different weight.  A flipped forward is un-flipped BEFORE its resize: the output column whose neighbours are x0, x1 reads the
 // columns w - 1 - x0 and w - 1 - x1 of image B + b.
-#include <string.h>
-#include "loss_common.hpp"
+#include "loss_common.hpp"               // uaps::pixel (the softmax of a pixel's logits), UAPS_BY_C, UAPS_LAUNCH_V
 #include "rn_math.hpp"
 
 namespace {
-using namespace uaps::loss;
+using uaps::kThreads; using uaps::kTooBig; using uaps::grid_for; using uaps::al16;
 constexpr int kMaxScales = UAPS_TTA_MAX_SCALES;
 constexpr int kMaxBlocks = 1 << 20;      // every tensor is below 2 GiB: a grid never needs more; the lanes stride over the rest anyway
 
@@ -150,10 +149,6 @@ __global__ __launch_bounds__(kThreads) void tta_fold_kernel(FoldArgs a) {
 inline float ratio(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 inline bool too_big(double elems, double bytes_each) { return elems * bytes_each >= kTooBig; }
 
-// the first version's structs end behind `stream`
-constexpr size_t kViewsV1 = offsetof(uaps_tta_views_call, stream) + sizeof(uaps_stream_t);
-constexpr size_t kFoldV1 = offsetof(uaps_tta_fold_call, stream) + sizeof(uaps_stream_t);
-
 template <int C>
 int launch_fold(const FoldArgs& a, bool vec, hipStream_t st) {
     const long groups = (long)a.B * a.H * a.W / (vec ? 4 : 1);
@@ -164,10 +159,8 @@ int launch_fold(const FoldArgs& a, bool vec, hipStream_t st) {
 }  // namespace
 
 extern "C" int uaps_tta_views(const uaps_tta_views_call* call) {
-    if (!call || call->struct_size < kViewsV1) return UAPS_EINVAL;
     uaps_tta_views_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kViewsV1);              // what a later header appends is not read
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if (!c.x || !c.out || (c.flip != 0 && c.flip != 1)) return UAPS_EINVAL;
     if (c.B <= 0 || c.Cin <= 0 || c.H <= 0 || c.W <= 0 || c.h <= 0 || c.w <= 0) return UAPS_EINVAL;
     const double planes = (double)c.B * c.Cin;
@@ -183,10 +176,8 @@ extern "C" int uaps_tta_views(const uaps_tta_views_call* call) {
 }
 
 extern "C" int uaps_tta_fold(const uaps_tta_fold_call* call) {
-    if (!call || call->struct_size < kFoldV1) return UAPS_EINVAL;
     uaps_tta_fold_call c;
-    memset(&c, 0, sizeof c);
-    memcpy(&c, call, kFoldV1);
+    if (uaps::read_call(call, c)) return UAPS_EINVAL;
     if ((!c.probs_sum && !c.mask && !c.conf) || (c.flip != 0 && c.flip != 1)) return UAPS_EINVAL;
     if (c.B <= 0 || c.C <= 0 || c.H <= 0 || c.W <= 0) return UAPS_EINVAL;
     if (c.C < 2 || c.C > UAPS_MAX_CLASSES || c.S < 1 || c.S > kMaxScales) return UAPS_ERANGE;

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._checks import TOO_BIG as _TOO_BIG
+from ._checks import check_instance_pair, pair_matrix_np, pair_operands
 from .instances import FIXED_ONE, InstanceResult
 
 COCO_THRESHOLDS = tuple(round(0.5 + 0.05 * i, 2) for i in range(10))
@@ -207,23 +207,15 @@ def _by_iou(a, b) -> int:
 
 
 def _detect_cpu(pred: InstanceResult, target: InstanceResult, Cn: int, t1000, agnostic: bool, max_dets, scores):
-    lp, lg = pred.labels.numpy(), target.labels.numpy()
     tp_, tg_ = pred.table.numpy(), target.table.numpy()
-    B, Mp, Mg, T = lp.shape[0], tp_.shape[1], tg_.shape[1], len(t1000)
+    B, Mp, Mg, T = tp_.shape[0], tp_.shape[1], tg_.shape[1], len(t1000)
     score = np.full((B, Mp), -np.inf, dtype=np.float64)
     rank = np.full((B, Mp), -1, dtype=np.int64)
     pm, pi = np.zeros((B, Mp, T), dtype=np.int64), np.zeros((B, Mp, T), dtype=np.int64)
     tm = np.zeros((B, Mg, T), dtype=np.int64)
     counts = np.zeros((B, Cn, T + 2), dtype=np.int64)
     for b in range(B):
-        np_, ng = max(0, min(int(pred.count[b]), Mp)), max(0, min(int(target.count[b]), Mg))
-        p, g = lp[b].reshape(-1).astype(np.int64), lg[b].reshape(-1).astype(np.int64)
-        sel = (p >= 1) & (p <= np_) & (g >= 1) & (g <= ng)
-        p, g = p[sel] - 1, g[sel] - 1
-        if not agnostic:
-            same = tp_[b, p, 0] == tg_[b, g, 0]
-            p, g = p[same], g[same]
-        inter = np.bincount(p * ng + g, minlength=np_ * ng).reshape(np_, ng) if np_ and ng else np.zeros((np_, ng), dtype=np.int64)
+        inter, np_, ng = pair_matrix_np(pred, target, b, agnostic)
         area_p, area_g = tp_[b, :np_, 1], tg_[b, :ng, 1]
         if scores is None:
             with np.errstate(divide="ignore", invalid="ignore"):
@@ -276,25 +268,14 @@ def detection_match(pred: InstanceResult, target: InstanceResult, num_classes: i
     by score descending, the lower label first on ties, and with max_dets = n only the first n take part.  Per image, class and
     threshold, in that order, a detection takes the free ground-truth defect of largest IoU among those that pass (the lowest number on
     ties) or is a false positive there; a ground-truth defect is taken at most once per threshold.  Does not synchronise."""
-    for r, what in ((pred, "pred"), (target, "target")):
-        if not isinstance(r, InstanceResult):
-            raise TypeError(f"detection_match: {what} is a result of label_instances")
-    if pred.labels.device != target.labels.device:
-        raise ValueError(f"detection_match: pred is on {pred.labels.device}, target on {target.labels.device}")
-    if pred.labels.shape != target.labels.shape:
-        raise ValueError(f"detection_match: pred labels {tuple(pred.labels.shape)}, target labels {tuple(target.labels.shape)}")
-    Cn = int(num_classes)
-    if not 1 <= Cn <= MAX_CLASSES:
-        raise ValueError(f"detection_match: 1 <= num_classes <= {MAX_CLASSES}")
+    B, H, W, Mp, Mg, Cn, valid = check_instance_pair("detection_match", pred, target, num_classes, MAX_CLASSES)
     t1000 = per_mille(iou_thresholds)
     if max_dets is not None:
         max_dets = int(max_dets)
         if max_dets < 1:
             raise ValueError("detection_match: max_dets is None or at least 1")
         max_dets = min(max_dets, 2 ** 31 - 1)
-    B, H, W = pred.labels.shape
-    Mp, Mg, T = pred.max_instances, target.max_instances, len(t1000)
-    dev = pred.labels.device
+    T, dev = len(t1000), pred.labels.device
     if scores is None:
         if pred.n_maps < 1:
             raise ValueError("detection_match: pred carries no map (label_instances(mask, maps=(confidence,))) and no scores are given")
@@ -306,17 +287,11 @@ def detection_match(pred: InstanceResult, target: InstanceResult, num_classes: i
         scores = scores.to(torch.float64).contiguous()
     if Mp > MAX_ROWS or Mg > MAX_ROWS:
         raise ValueError(f"detection_match: max_instances <= {MAX_ROWS} on both sides")
-    if H * W >= _TOO_BIG:
-        raise ValueError("detection_match: H*W < 2^31")
-    if B * Mp * Mg * 4 >= _TOO_BIG:
-        raise ValueError(f"detection_match: the dense pair matrix of B * {Mp} * {Mg} * 4 bytes reaches 2 GiB: lower max_instances")
-    valid = ~(pred.overflow | target.overflow)
     agnostic, from_map = bool(class_agnostic), scores is None
     if not pred.labels.is_cuda:
         out = _detect_cpu(pred, target, Cn, t1000, agnostic, max_dets, None if scores is None else scores.numpy())
         return DetectionResult(*out, valid, t1000, agnostic, from_map, pred, target)
-    held = {side + "_" + name: getattr(r, name).contiguous() for side, r in (("pred", pred), ("target", target))
-            for name in ("labels", "count", "table")}
+    held = pair_operands(pred, target)
     score = torch.empty((B, Mp), dtype=torch.float64, device=dev)
     rank = torch.empty((B, Mp), dtype=torch.int64, device=dev)
     pm = torch.empty((B, Mp, T), dtype=torch.int64, device=dev)

@@ -31,8 +31,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._checks import TOO_BIG as _TOO_BIG
-from .instances import InstanceResult
+from ._checks import TOO_BIG as _TOO_BIG, check_instances
+from .instances import InstanceResult, add_props, host_tables
 
 HULL_COLUMNS = ("nv", "area2", "fmax_sq", "f_y0", "f_x0", "f_y1", "f_x1", "w_ey", "w_ex", "w_c",
                 "r_y", "r_x", "r_ey", "r_ex", "r_dmin", "r_dmax", "r_c")
@@ -59,11 +59,6 @@ class HullResult(NamedTuple):
     instances: InstanceResult
     also: Optional[object] = None
 
-    def _host(self):
-        B, M = self.table.shape[:2]
-        packed = torch.cat([self.table.reshape(B, -1), self.instances.table.reshape(B, -1)], dim=1).cpu().numpy()
-        return packed[:, :M * 17].reshape(B, M, 17), packed[:, M * 17:].reshape(B, M, 9)
-
     def props(self) -> Dict[str, np.ndarray]:
         """One device-to-host copy; a dict of float64 arrays [B,max_instances], NaN in rows without a component.  Every value is a
         few correctly rounded float64 operations on the exact integers; with A = area, E = w_ex^2 + w_ey^2 of the width edge,
@@ -76,7 +71,7 @@ class HullResult(NamedTuple):
           rect_angle: the longer side's -- the edge's where D >= r_c, else its normal's
           rect_cy = (2 F r_y + (r_dmin + r_dmax) r_ey + r_c r_ex) / (2 F),  rect_cx = (2 F r_x + (r_dmin + r_dmax) r_ex - r_c r_ey) / (2 F)
           rectangularity = A F / (D r_c)"""
-        hl, tb = self._host()
+        hl, tb = host_tables(self.table, self.instances)
         B, M = hl.shape[:2]
         out = {n: np.full((B, M), np.nan, dtype=np.float64) for n in PROPS}
         for b in range(B):
@@ -106,7 +101,7 @@ class HullResult(NamedTuple):
         """One device-to-host copy; float64 [B,max_instances,4,2]: the minimum-area rectangle's corners as (y, x), in hull order
         (from the corner behind the edge's start along the edge, then across the defect), for drawing; NaN in rows without a
         component.  The corner at (d, c) is (r_y, r_x) + (d (r_ey, r_ex) + c (r_ex, -r_ey)) / F, each coordinate one division."""
-        hl, tb = self._host()
+        hl, tb = host_tables(self.table, self.instances)
         B, M = hl.shape[:2]
         out = np.full((B, M, 4, 2), np.nan, dtype=np.float64)
         for b in range(B):
@@ -122,14 +117,7 @@ class HullResult(NamedTuple):
 
     def records(self) -> List[List[dict]]:
         """instances.records() -- also.records() where `also` is attached -- with every key of props() added to each defect."""
-        recs = self.also.records() if self.also is not None else self.instances.records()
-        p = self.props()
-        for b, rows in enumerate(recs):
-            for r in rows:
-                k = r["label"] - 1
-                for name, arr in p.items():
-                    r[name] = float(arr[b, k])
-        return recs
+        return add_props(self.also.records() if self.also is not None else self.instances.records(), self.props())
 
 
 def _strict_chain(points):
@@ -212,19 +200,7 @@ def hull_descriptors(inst: InstanceResult) -> HullResult:
     The hull is that of the label's pixels wherever they are: the instance table's box is not consulted.
     1 <= H, W <= 4096, B*H*W*8 < 2 GiB, and a table and a workspace (B * max_instances * (H + 1) * 8 bytes) below 2 GiB.
     Does not synchronise with the host."""
-    if not isinstance(inst, InstanceResult):
-        raise TypeError("hull_descriptors: an instances.InstanceResult expected")
-    labels = inst.labels
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or labels.dtype != torch.int32:
-        raise TypeError("hull_descriptors: int32 [B,H,W] labels expected")
-    B, H, W = labels.shape
-    M = int(inst.max_instances)
-    if inst.table.dim() != 3 or inst.table.shape[0] != B or inst.table.shape[2] != 9:
-        raise TypeError("hull_descriptors: the instance table is int64 [B,max_instances,9]")
-    if B < 1 or H < 1 or W < 1 or M < 1:
-        raise ValueError("hull_descriptors: empty labels")
-    if H > MAX_EXTENT or W > MAX_EXTENT:
-        raise ValueError(f"hull_descriptors: H and W up to {MAX_EXTENT}")
+    labels, B, H, W, M = check_instances("hull_descriptors", inst, MAX_EXTENT)
     if B * H * W * 8 >= _TOO_BIG or B * M * 136 >= _TOO_BIG or B * M * (H + 1) * 8 + 256 >= _TOO_BIG:
         raise ValueError("hull_descriptors: B*H*W*8 < 2 GiB, and a table and a workspace below 2 GiB")
     labels = labels.detach().contiguous()

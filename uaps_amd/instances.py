@@ -68,6 +68,23 @@ class InstanceResult(NamedTuple):
         return out
 
 
+def host_tables(table: torch.Tensor, inst: InstanceResult) -> Tuple[np.ndarray, np.ndarray]:
+    """One device-to-host copy of a descriptor table [B,M,K] packed beside the instance table: (int64 [B,M,K], int64 [B,M,9])."""
+    B, M, K = table.shape
+    packed = torch.cat([table.reshape(B, -1), inst.table.reshape(B, -1)], dim=1).cpu().numpy()
+    return packed[:, :M * K].reshape(B, M, K), packed[:, M * K:].reshape(B, M, 9)
+
+
+def add_props(records: List[List[dict]], props) -> List[List[dict]]:
+    """Every key of a props() dict (arrays [B,max_instances]) added to each defect's dict of records(), in place."""
+    for b, rows in enumerate(records):
+        for r in rows:
+            k = r["label"] - 1
+            for name, arr in props.items():
+                r[name] = float(arr[b, k])
+    return records
+
+
 def fixed_point(v: np.ndarray) -> np.ndarray:
     """q(v) of the table's sums on the host: int64, NaN -> 0.  Scaling by 2^24 is exact in fp32 and the product is below 2^41."""
     v = np.asarray(v, dtype=np.float32)

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._checks import TOO_BIG as _TOO_BIG
+from ._checks import check_instance_pair, pair_matrix_np, pair_operands
 from .instances import InstanceResult
 
 MATCH_COLUMNS = ("partner", "inter", "covered", "matched")
@@ -171,22 +171,13 @@ def _reduce_np(inter: np.ndarray, axis: int, area_mine: np.ndarray, area_other: 
 
 
 def _match_cpu(pred: InstanceResult, target: InstanceResult, Cn: int, thr: float, agnostic: bool):
-    lp, lg = pred.labels.numpy(), target.labels.numpy()
     tp_, tg_ = pred.table.numpy(), target.table.numpy()
-    B = lp.shape[0]
-    Mp, Mg = tp_.shape[1], tg_.shape[1]
+    B, Mp, Mg = tp_.shape[0], tp_.shape[1], tg_.shape[1]
     out_p = np.zeros((B, Mp, 4), dtype=np.int64)
     out_g = np.zeros((B, Mg, 4), dtype=np.int64)
     counts = np.zeros((B, Cn, 3), dtype=np.int64)
     for b in range(B):
-        np_, ng = min(int(pred.count[b]), Mp), min(int(target.count[b]), Mg)
-        p, g = lp[b].reshape(-1).astype(np.int64), lg[b].reshape(-1).astype(np.int64)
-        sel = (p >= 1) & (p <= Mp) & (g >= 1) & (g <= Mg)
-        p, g = p[sel] - 1, g[sel] - 1
-        if not agnostic:
-            same = tp_[b, p, 0] == tg_[b, g, 0]
-            p, g = p[same], g[same]
-        inter = np.bincount(p * ng + g, minlength=np_ * ng).reshape(np_, ng) if np_ and ng else np.zeros((np_, ng), dtype=np.int64)
+        inter, np_, ng = pair_matrix_np(pred, target, b, agnostic)
         out_p[b, :np_] = _reduce_np(inter, 1, tp_[b, :np_, 1], tg_[b, :ng, 1], thr)
         out_g[b, :ng] = _reduce_np(inter, 0, tg_[b, :ng, 1], tp_[b, :np_, 1], thr)
         for c in range(Cn):
@@ -203,31 +194,15 @@ def match_instances(pred: InstanceResult, target: InstanceResult, num_classes: i
     class (class_agnostic: of any classes), adds 1 to inter[b, p, g]; p and g are matched iff
     float64(inter) > float64(iou_threshold) * float64(area_p + area_g - inter).  Only 0.5 <= iou_threshold < 1 is accepted (below
     0.5 a match is not unique and needs an assignment step).  Does not synchronise with the host."""
-    for r, what in ((pred, "pred"), (target, "target")):
-        if not isinstance(r, InstanceResult):
-            raise TypeError(f"match_instances: {what} is a result of label_instances")
-    if pred.labels.device != target.labels.device:
-        raise ValueError(f"match_instances: pred is on {pred.labels.device}, target on {target.labels.device}")
-    if pred.labels.shape != target.labels.shape:
-        raise ValueError(f"match_instances: pred labels {tuple(pred.labels.shape)}, target labels {tuple(target.labels.shape)}")
-    Cn, thr = int(num_classes), float(iou_threshold)
-    if not 1 <= Cn <= MAX_CLASSES:
-        raise ValueError(f"match_instances: 1 <= num_classes <= {MAX_CLASSES}")
+    B, H, W, Mp, Mg, Cn, valid = check_instance_pair("match_instances", pred, target, num_classes, MAX_CLASSES)
+    thr = float(iou_threshold)
     if not 0.5 <= thr < 1.0:
         raise ValueError("match_instances: 0.5 <= iou_threshold < 1 (a lower threshold needs an assignment step, which is not built)")
-    B, H, W = pred.labels.shape
-    Mp, Mg = pred.max_instances, target.max_instances
-    if H * W >= _TOO_BIG:
-        raise ValueError("match_instances: H*W < 2^31")
-    if B * Mp * Mg * 4 >= _TOO_BIG:
-        raise ValueError(f"match_instances: the dense pair matrix of B * {Mp} * {Mg} * 4 bytes reaches 2 GiB: lower max_instances")
-    valid = ~(pred.overflow | target.overflow)
     if not pred.labels.is_cuda:
         out_p, out_g, counts = _match_cpu(pred, target, Cn, thr, bool(class_agnostic))
         return MatchResult(out_p, out_g, counts, valid, thr, pred, target)
     dev = pred.labels.device
-    held = {side + "_" + name: getattr(r, name).contiguous() for side, r in (("pred", pred), ("target", target))
-            for name in ("labels", "count", "table")}
+    held = pair_operands(pred, target)
     out_p = torch.empty((B, Mp, 4), dtype=torch.int64, device=dev)
     out_g = torch.empty((B, Mg, 4), dtype=torch.int64, device=dev)
     counts = torch.empty((B, Cn, 3), dtype=torch.int64, device=dev)

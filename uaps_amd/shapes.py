@@ -32,8 +32,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._checks import TOO_BIG as _TOO_BIG
-from .instances import InstanceResult
+from ._checks import TOO_BIG as _TOO_BIG, check_instances, check_plane
+from .instances import InstanceResult, add_props, host_tables
 
 SHAPE_COLUMNS = ("sy", "sx", "syy", "sxy", "sxx", "q1", "q2", "q3", "qd", "pmax", "psum")
 MAX_EXTENT = _lib.SHAPE_MAX_EXTENT
@@ -70,11 +70,8 @@ class ShapeResult(NamedTuple):
         N11 = A sxy - sx sy, disc = (N20 - N02)^2 + 4 N11^2 and det = N20 N02 - N11^2,
           var_x = N20 / A^2, var_y = N02 / A^2, cov_xy = N11 / A^2, l1 = (N20 + N02 + sqrt(disc)) / (2 A^2), l2 = det / (A^4 l1)
         (the product form: no subtraction of nearly equal numbers), 0 where l1 = 0."""
-        B, M = self.table.shape[:2]
-        inst = self.instances
-        packed = torch.cat([self.table.reshape(B, -1), inst.table.reshape(B, -1)], dim=1).cpu().numpy()
-        sh = packed[:, :M * 11].reshape(B, M, 11)
-        tb = packed[:, M * 11:].reshape(B, M, 9)
+        sh, tb = host_tables(self.table, self.instances)
+        B, M = sh.shape[:2]
         names = ["centroid_y", "centroid_x", "var_x", "var_y", "cov_xy", "l1", "l2", "major_axis", "minor_axis", "eccentricity",
                  "orientation", "perimeter_crack", "perimeter", "compactness", "euler", "holes", "extent", "equivalent_diameter"]
         if self.has_plane != "none":
@@ -119,14 +116,7 @@ class ShapeResult(NamedTuple):
 
     def records(self) -> List[List[dict]]:
         """instances.records() with every key of props() added to each defect's dict (two device-to-host copies)."""
-        recs = self.instances.records()
-        p = self.props()
-        for b, rows in enumerate(recs):
-            for r in rows:
-                k = r["label"] - 1
-                for name, arr in p.items():
-                    r[name] = float(arr[b, k])
-        return recs
+        return add_props(self.instances.records(), self.props())
 
 
 def _shapes_cpu(labels: np.ndarray, plane: Optional[np.ndarray], M: int) -> np.ndarray:
@@ -181,21 +171,9 @@ def shape_descriptors(inst: InstanceResult, plane: Optional[torch.Tensor] = None
     defect.  Where defects of different classes touch it is the thickness of their union; an image every pixel of which belongs
     to a component has no such pixel and gets surface.NO_FEATURE.  distance_transform_sq limits H and W to 4096.
     1 <= H, W <= 16384 and label_instances' limits.  Does not synchronise with the host."""
-    if not isinstance(inst, InstanceResult):
-        raise TypeError("shape_descriptors: an instances.InstanceResult expected")
-    labels = inst.labels
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or labels.dtype != torch.int32:
-        raise TypeError("shape_descriptors: int32 [B,H,W] labels expected")
+    labels, B, H, W, M = check_instances("shape_descriptors", inst, MAX_EXTENT)
     if connectivity not in (4, 8):
         raise ValueError("shape_descriptors: connectivity is 4 or 8")
-    B, H, W = labels.shape
-    M = int(inst.max_instances)
-    if inst.table.dim() != 3 or inst.table.shape[0] != B or inst.table.shape[2] != 9:
-        raise TypeError("shape_descriptors: the instance table is int64 [B,max_instances,9]")
-    if B < 1 or H < 1 or W < 1 or M < 1:
-        raise ValueError("shape_descriptors: empty labels")
-    if H > MAX_EXTENT or W > MAX_EXTENT:
-        raise ValueError(f"shape_descriptors: H and W up to {MAX_EXTENT}")
     if H * W >= _TOO_BIG or B * H * W * 8 >= _TOO_BIG or B * M * 88 >= _TOO_BIG:
         raise ValueError("shape_descriptors: H*W < 2^31, B*H*W*8 < 2 GiB and a table below 2 GiB")
     kind = "none"
@@ -205,9 +183,7 @@ def shape_descriptors(inst: InstanceResult, plane: Optional[torch.Tensor] = None
         from .surface import distance_transform_sq
         plane, kind = distance_transform_sq(labels), "thickness"
     elif plane is not None:
-        if not isinstance(plane, torch.Tensor) or plane.dtype != torch.int32 or plane.shape != labels.shape or plane.device != labels.device:
-            raise TypeError("shape_descriptors: the plane is an int32 [B,H,W] tensor on the labels' device")
-        kind = "plane"
+        plane, kind = check_plane("shape_descriptors", plane, labels), "plane"
     labels = labels.detach().contiguous()
     plane = None if plane is None else plane.detach().contiguous()
     if not labels.is_cuda:

@@ -30,8 +30,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._checks import TOO_BIG as _TOO_BIG, check_classes
-from .instances import InstanceResult
+from ._checks import TOO_BIG as _TOO_BIG, check_classes, check_instances, check_plane
+from .instances import InstanceResult, add_props, host_tables
 
 SKELETON_COLUMNS = ("n_skel", "n_orth", "n_diag", "n_end", "n_branch", "d2max", "d2sum")
 MAX_CLASSES, MAX_ITERS, MAX_SUB_ITERS, MAX_EXTENT = _lib.SKEL_MAX_CLASSES, _lib.SKEL_MAX_ITERS, _lib.SKEL_MAX_SUB_ITERS, _lib.SKEL_MAX_EXTENT
@@ -161,11 +161,8 @@ class SkeletonStats(NamedTuple):
           width_mean = area / (length + 1): a straight one-pixel line has width 1
           width_max = 2 sqrt(d2max) - 1 and width_rms = 2 sqrt(d2sum / n_skel) - 1 (with a plane; NaN where n_skel == 0, which
           happens when the skeleton was cut by classes)."""
-        B, M = self.table.shape[:2]
-        inst = self.instances
-        packed = torch.cat([self.table.reshape(B, -1), inst.table.reshape(B, -1)], dim=1).cpu().numpy()
-        sk = packed[:, :M * 7].reshape(B, M, 7)
-        tb = packed[:, M * 7:].reshape(B, M, 9)
+        sk, tb = host_tables(self.table, self.instances)
+        B, M = sk.shape[:2]
         names = ["length", "endpoints", "branch_points", "width_mean", "skeleton_pixels"]
         if self.has_plane:
             names += ["width_max", "width_rms"]
@@ -189,14 +186,7 @@ class SkeletonStats(NamedTuple):
 
     def records(self) -> List[List[dict]]:
         """instances.records() -- shapes.records() where `shapes` is attached -- with every key of props() added to each defect."""
-        recs = self.shapes.records() if self.shapes is not None else self.instances.records()
-        p = self.props()
-        for b, rows in enumerate(recs):
-            for r in rows:
-                k = r["label"] - 1
-                for name, arr in p.items():
-                    r[name] = float(arr[b, k])
-        return recs
+        return add_props(self.shapes.records() if self.shapes is not None else self.instances.records(), self.props())
 
 
 def _stats_cpu(labels: np.ndarray, skel: np.ndarray, classes, plane: Optional[np.ndarray], M: int) -> np.ndarray:
@@ -241,29 +231,18 @@ def skeleton_descriptors(inst: InstanceResult, skel: SkeletonResult, *, thicknes
     distance transform, for tests.)"""
     if not isinstance(inst, InstanceResult) or not isinstance(skel, SkeletonResult):
         raise TypeError("skeleton_descriptors: an instances.InstanceResult and a SkeletonResult expected")
-    labels, sk = inst.labels, skel.mask
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or labels.dtype != torch.int32:
-        raise TypeError("skeleton_descriptors: int32 [B,H,W] labels expected")
+    labels, B, H, W, M = check_instances("skeleton_descriptors", inst, _lib.SHAPE_MAX_EXTENT)
+    sk = skel.mask
     if not isinstance(sk, torch.Tensor) or sk.dtype != torch.int64 or sk.shape != labels.shape or sk.device != labels.device:
         raise TypeError("skeleton_descriptors: the skeleton is an int64 map of the labels' shape on their device")
-    B, H, W = labels.shape
-    M = int(inst.max_instances)
     classes = tuple(int(c) for c in skel.classes)
     if not 1 <= len(classes) <= MAX_CLASSES:
         raise ValueError(f"skeleton_descriptors: 1..{MAX_CLASSES} skeleton classes")
-    if inst.table.dim() != 3 or inst.table.shape[0] != B or inst.table.shape[2] != 9:
-        raise TypeError("skeleton_descriptors: the instance table is int64 [B,max_instances,9]")
-    if B < 1 or H < 1 or W < 1 or M < 1:
-        raise ValueError("skeleton_descriptors: empty labels")
-    if H > _lib.SHAPE_MAX_EXTENT or W > _lib.SHAPE_MAX_EXTENT:
-        raise ValueError(f"skeleton_descriptors: H and W up to {_lib.SHAPE_MAX_EXTENT}")
     if H * W >= _TOO_BIG or B * H * W * 8 >= _TOO_BIG or B * M * 56 >= _TOO_BIG:
         raise ValueError("skeleton_descriptors: H*W < 2^31, B*H*W*8 < 2 GiB and a table below 2 GiB")
     plane = None
     if _plane is not None:
-        if not isinstance(_plane, torch.Tensor) or _plane.dtype != torch.int32 or _plane.shape != labels.shape or _plane.device != labels.device:
-            raise TypeError("skeleton_descriptors: the plane is an int32 [B,H,W] tensor on the labels' device")
-        plane = _plane
+        plane = check_plane("skeleton_descriptors", _plane, labels)
     elif thickness:
         from .surface import distance_transform_sq
         plane = distance_transform_sq(labels)

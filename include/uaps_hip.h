@@ -2136,6 +2136,80 @@ int uaps_contours_simplify_workspace_bytes(int64_t n_points, int64_t n_rings, si
 int uaps_contours_simplify_mark(const uaps_simplify_call* call);
 int uaps_contours_simplify_write(const uaps_simplify_call* call);
 
+/* ---------------------------------------------------------------------------------------------
+ * Polygon rasterisation: csrc/raster.hip.
+ *
+ * uaps_raster_plan / uaps_raster_fill: the exact even-odd fill of polygon rings into a label map -- the inverse of
+ *   uaps_contours_trace / _write; integers only, the same bits from run to run and from both edge forms.
+ *   Inputs: points int32 [n_points, 2] (y, x) in units of 2^-frac_bits pixel, 0 <= y, x <= UAPS_RASTER_MAX_EXTENT << frac_bits
+ *   (values outside are clamped into that range); ring_offsets int32 [n_rings + 1]; rings int64 [n_rings, ring_stride] with the
+ *   image in column 0 and the label in column 1 (ring_stride 7: the rings of uaps_contours_write and uaps_contours_simplify_write).
+ *   A ring of n points has n edges, the last one closes it; rings of fewer than 3 points, of an image outside [0, B) or of a label
+ *   outside [1, max_instances] contribute nothing.  Rings may reach outside the H x W frame.
+ *   Pixel (r, c) is sampled at its centre (r + 1/2, c + 1/2).  In doubled units with s = 2^frac_bits a row's centre is
+ *   Yc = (2 r + 1) s; an edge A -> B crosses row r iff min(2 ya, 2 yb) <= Yc < max(2 ya, 2 yb) (half-open: a vertex on a centre
+ *   row counts once, horizontal edges never cross); with (Y0, X0) the doubled endpoint of smaller Y, dy > 0 and dx the doubled
+ *   differences to the other one and num = X0 dy + (Yc - Y0) dx, the first column at or right of the crossing is
+ *   c0 = ceil((num - s dy) / (2 s dy)) clamped to [0, W] (a centre exactly on an edge counts as right of it; c0 = W toggles nothing).
+ *   Even-odd per label: pixel (r, c) belongs to label k iff the number of crossings of k's edges in row r with c0 <= c is odd.
+ *     labels   int64 [B, H, W]                the lowest label that owns the pixel, `background` where none does
+ *     mask     int64 [B, H, W]                with classes (int64 [B, max_instances]): classes[b][label - 1], 0 where no label owns it
+ *     stats    int64 [B, max_instances, 2]    area (the pixels the label owns, whatever other labels own them too), inter (those of
+ *                                             them where reference == label; 0 without a reference)
+ *     overlap  int64 [B]                      the pixels owned by more than one label
+ *     totals   int64 [4]                      the 64-bit words of all bit planes, the labels with a word, their box rows, 0
+ *   uaps_raster_plan finds the box of every label's ring points clipped to the frame -- rows x 64-bit words, one bit a pixel --
+ *   scans the words into offsets and fills `totals` (on the device); it does not synchronise.  The caller reads totals[0], provides
+ *   `planes` of that many words and passes n_words to uaps_raster_fill, which fills the outputs from the SAME, untouched workspace:
+ *   planes cleared, every row an edge crosses toggles bit c0 of the label's box row (64-bit atomic XOR), a prefix XOR along every
+ *   box row, set pixels to a paint plane by atomicMin, the paint plane to labels.  ring_offsets is not validated: points that no
+ *   ring [ring_offsets[r], ring_offsets[r + 1]) inside [0, n_points] holds are left out, silently.  With totals[0] = 0 no pixel is owned and there
+ *   is nothing to fill (n_words < 1 is refused).  A workspace whose total is not the one passed makes the launches store nothing.
+ *   edge_wave_rows: an edge that crosses more rows than this goes on a list that a second launch deals to whole waves, an edge a
+ *   wave; 0 = the default (UAPS_RASTER_WAVE_ROWS),
+ *   UAPS_RASTER_ALL_WAVE = every edge; it changes the time, never a bit.
+ *   workspace: uaps_raster_workspace_bytes(n_points, n_rings, B, H, W, max_instances): 8 bytes a point, 4 a pixel and 24 an
+ *   (image, label) pair, 256-byte aligned, the pair of calls' alone from plan until fill has run; it need not be zeroed.
+ * Errors (nothing launched, outputs untouched): UAPS_EINVAL null struct, points, ring_offsets, rings or workspace or two of the three
+ *   equal, non-positive dimension, max_instances < 1, n_points or n_rings < 1, frac_bits outside 0 .. UAPS_RASTER_MAX_FRAC_BITS,
+ *   ring_stride outside 2 .. 64, edge_wave_rows outside UAPS_RASTER_ALL_WAVE .. UAPS_RASTER_MAX_EXTENT, struct_size below this
+ *   version's, plan: null totals or totals equal to an input, fill: null planes, labels, stats or overlap, classes without mask or
+ *   mask without classes, an output equal to an input or to another output, n_words < 1 (the query: a NULL result pointer);
+ *   UAPS_ERANGE H or W above UAPS_RASTER_MAX_EXTENT, n_points or n_rings of 2^30 or more, labels (B * H * W * 8) or the sums
+ *   (B * max_instances * 16) of 2 GiB or more, fill: planes (n_words * 8) of 2 GiB or more; UAPS_EWORKSPACE a workspace smaller than
+ *   the query's answer or not 256-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_RASTER_COLUMNS 2
+#define UAPS_RASTER_MAX_EXTENT 4096
+#define UAPS_RASTER_MAX_FRAC_BITS 4
+#define UAPS_RASTER_WAVE_ROWS 64
+#define UAPS_RASTER_ALL_WAVE (-1)
+typedef struct uaps_raster_call {
+    uint32_t struct_size;
+    int32_t B, H, W, max_instances;
+    int32_t frac_bits, ring_stride, edge_wave_rows;
+    int64_t n_points, n_rings;
+    const int32_t* points;                       /* [n_points][2] */
+    const int32_t* ring_offsets;                 /* [n_rings + 1] */
+    const int64_t* rings;                        /* [n_rings][ring_stride] */
+    int64_t* totals;                             /* plan: [4] on the device */
+    int64_t n_words;                             /* fill: totals[0] as read */
+    uint64_t* planes;                            /* fill: [n_words], the caller's; holds nothing of use afterwards */
+    const int32_t* reference;                    /* fill: [B][H][W] or NULL */
+    const int64_t* classes;                      /* fill: [B][max_instances] or NULL */
+    int64_t background;                          /* fill */
+    int64_t* labels;                             /* fill: [B][H][W], written whole */
+    int64_t* mask;                               /* fill: [B][H][W], written whole; with classes */
+    int64_t* stats;                              /* fill: [B][max_instances][2], written whole */
+    int64_t* overlap;                            /* fill: [B], written whole */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_raster_call;
+int uaps_raster_workspace_bytes(int64_t n_points, int64_t n_rings, int B, int H, int W, int max_instances, size_t* bytes);
+int uaps_raster_plan(const uaps_raster_call* call);
+int uaps_raster_fill(const uaps_raster_call* call);
+
 #ifdef __cplusplus
 }
 #endif

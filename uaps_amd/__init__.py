@@ -70,6 +70,11 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
   simplify_contours, SimplifiedContours             contour simplification: exact Ramer-Douglas-Peucker on those rings at a tolerance
                                                     in sixteenths of a pixel, integers only; polygons(), records(), to_coco(),
                                                     reduction(); inference.predict_instances(..., contours=True, simplify=epsilon)
+  rasterize_contours, RasterResult, RingSet, rings_from_polygons, rings_from_coco, RASTER_COLUMNS
+                                                    polygon rasterisation: the exact even-odd fill of polygon rings (traced,
+                                                    simplified, or COCO / labelme ground truth in sixteenths of a pixel) into a
+                                                    label map and a class map, integers only; RasterResult.iou(), fidelity(),
+                                                    records(); inference.predict_instances(..., contours=True, raster=True)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -116,6 +121,8 @@ from . import hull
 from .contours import contours, ContourResult, RING_COLUMNS, CONTOUR_COLUMNS      # (the function takes the submodule's name)
 from .simplify import simplify_contours, SimplifiedContours
 from . import simplify
+from .raster import rasterize_contours, RasterResult, RingSet, rings_from_polygons, rings_from_coco, RASTER_COLUMNS
+from . import raster
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

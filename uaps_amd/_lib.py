@@ -203,6 +203,9 @@ SIGNATURES = {
     "uaps_contours_simplify_workspace_bytes": (C.c_int, [C.c_int64, C.c_int64, C.POINTER(C.c_size_t)]),
     "uaps_contours_simplify_mark": (C.c_int, [_PTR]),
     "uaps_contours_simplify_write": (C.c_int, [_PTR]),
+    "uaps_raster_workspace_bytes": (C.c_int, [C.c_int64, C.c_int64] + [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
+    "uaps_raster_plan": (C.c_int, [_PTR]),
+    "uaps_raster_fill": (C.c_int, [_PTR]),
 }
 
 
@@ -470,6 +473,20 @@ class SimplifyCall(C.Structure):
                 ("summary_out", C.c_void_p), ("totals", C.c_void_p), ("n_points_out", C.c_int64), ("ring_capacity", C.c_int64),
                 ("point_capacity", C.c_int64), ("points_out", C.c_void_p), ("ring_offsets_out", C.c_void_p), ("rings_out", C.c_void_p),
                 ("ring_stats", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+RASTER_COLUMNS, RASTER_MAX_EXTENT, RASTER_MAX_FRAC_BITS, RASTER_WAVE_ROWS, RASTER_ALL_WAVE = 2, 4096, 4, 64, -1     # UAPS_RASTER_*
+
+
+class RasterCall(C.Structure):
+    """uaps_raster_call (include/uaps_hip.h): every operand of uaps_raster_plan and uaps_raster_fill, size-versioned."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("max_instances", C.c_int32),
+                ("frac_bits", C.c_int32), ("ring_stride", C.c_int32), ("edge_wave_rows", C.c_int32), ("n_points", C.c_int64),
+                ("n_rings", C.c_int64), ("points", C.c_void_p), ("ring_offsets", C.c_void_p), ("rings", C.c_void_p),
+                ("totals", C.c_void_p), ("n_words", C.c_int64), ("planes", C.c_void_p), ("reference", C.c_void_p),
+                ("classes", C.c_void_p), ("background", C.c_int64), ("labels", C.c_void_p), ("mask", C.c_void_p),
+                ("stats", C.c_void_p), ("overlap", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
 
 
 TILE_MAX_CHUNKS, TILE_MAX_MAPS = 32, 2  # UAPS_TILE_MAX_CHUNKS, UAPS_TILE_MAX_MAPS

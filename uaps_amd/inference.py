@@ -251,7 +251,7 @@ def _with_shapes(inst, shapes, connectivity: int):
 @torch.no_grad()
 def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, tiled=None, min_area: int = 1, connectivity: int = 8,
                       max_instances: int = 256, cleanup=None, components=None, shapes=False, skeleton=False, hull=False,
-                      contours=False, simplify=None):
+                      contours=False, simplify=None, raster=False):
     """Defects instead of pixels: instances.label_instances on the main head's arg-max mask, with maps = (confidence, uncertainty).
     The confidence is the main head's largest softmax; with tta (True, or a tuple of scales) mask and confidence are those of
     tta.predict_tta.  The uncertainty is consistency.uncertainty_map(main, aux1) of the plain forward where the model has an auxiliary
@@ -276,8 +276,15 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     the ring counts and the crack perimeter to theirs.  Under all three paths, after both clean-up chains.
     simplify=epsilon (a float, pixels; needs contours=True): a simplify.SimplifiedContours instead -- simplify.simplify_contours of
     that ContourResult at the tolerance epsilon, the staircases of slanted edges reduced to their corners; its `.source` is the
-    ContourResult.  Under all three paths."""
+    ContourResult.  Under all three paths.
+    raster=True (needs contours=True): a raster.RasterResult instead -- raster.rasterize_contours of what the same call returns
+    without raster= (the ContourResult, or with simplify= the SimplifiedContours), filled against the instance labels: its
+    `.contours` holds that result, iou() and fidelity() say what every polygon still covers of its defect.  Under all three paths."""
     from . import instances
+    if raster is not False and raster is not True:
+        raise ValueError("predict_instances: raster is False or True")
+    if raster and not contours:
+        raise ValueError("predict_instances: raster needs contours=True")
     if contours is not False and contours is not True:
         raise ValueError("predict_instances: contours is False or True")
     if simplify is not None:
@@ -323,10 +330,13 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
         return res
     from .contours import contours as trace_contours
     traced = trace_contours(inst, connectivity)._replace(also=None if res is inst else res)
-    if simplify is None:
+    if simplify is not None:
+        from .simplify import simplify_contours
+        traced = simplify_contours(traced, simplify)
+    if not raster:
         return traced
-    from .simplify import simplify_contours
-    return simplify_contours(traced, simplify)
+    from .raster import rasterize_contours
+    return rasterize_contours(traced, reference=True)
 
 
 def load_for_inference(model: torch.nn.Module, checkpoint_path: str, device: Optional[torch.device] = None) -> Dict:

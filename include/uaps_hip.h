@@ -1463,6 +1463,57 @@ int uaps_components_workspace_bytes(int B, int H, int W, int n_classes, size_t* 
 int uaps_components(const uaps_components_call* call);
 
 /* ---------------------------------------------------------------------------------------------
+ * Hysteresis thresholding and binary reconstruction: csrc/hysteresis.hip (the labelling passes: csrc/cc_common.hpp).
+ *
+ * uaps_hysteresis: the seeded components of a score map, or of a label map and a marker map.  out int64 [B, H, W], any H, W >= 1.
+ *   classes[0 .. n_classes) are the selected classes, strictly ascending, none equal to `background`.
+ *   Score form (scores != NULL; mask and markers NULL): scores fp32 [B, C, H, W], 1 <= C <= UAPS_MAX_CLASSES.  from_logits: the
+ *     softmax over all C channels is formed in the kernel (C == 1: the sigmoid 1 / (1 + exp(-z))).  classes lie in [0, C); C == 1:
+ *     the one channel is the score of class 1 and classes = {1}.  A pixel's class c* is the arg-max of its scores over the SELECTED
+ *     classes alone (the lowest class among equal scores); it is a CANDIDATE of c* iff s[c*] >= low[k*] and a SEED iff
+ *     s[c*] >= high[k*], k* the place of c* in `classes`, compared in fp32.  A pixel with a NaN among its selected scores is neither.
+ *     Components are maximal sets of candidates of one class connected under `connectivity` (4 or 8).  A component survives iff it
+ *     holds a seed and has at least min_area pixels.  out: the class on surviving pixels, `background` elsewhere.
+ *   Marker form (scores == NULL): mask int64 [B, H, W], markers uint8 [B, H, W] (non-zero: seed), out != mask; C, from_logits, low and
+ *     high are not read.  A component of a selected class of `mask` survives iff one of its own pixels has a non-zero marker and it
+ *     has at least min_area pixels; dropped pixels become `background`; every other value (ignore labels, unselected classes)
+ *     passes through untouched, and a marker on such a pixel marks nothing.
+ *   Launches: a classify pass writes an int64 code map into the workspace (class + 1 in the low word, 0: forms nothing; bit 32: seed);
+ *   tile-local union-find in LDS and seam merging with agent-scope atomics on that map (one labelling for all classes); flatten +
+ *   area with the seed raising bit 31 of the root's area word; one apply pass that writes `out` once.  Integer atomics only: the same
+ *   bits from run to run.  No workgroup waits for another inside a launch.  The call does not synchronise; the area and flag words
+ *   are zeroed inside the call.
+ *   workspace: uaps_hysteresis_workspace_bytes(B, H, W) bytes (16 a pixel), 256-byte aligned, the call's alone until it has run.
+ * Errors (nothing launched): UAPS_EINVAL null struct, out or workspace, neither or both forms' operands, out == mask, non-positive
+ *   dimension, n_classes outside [1, 8], classes not strictly ascending, negative or equal to `background`, a class outside [0, C)
+ *   (C == 1: other than 1), from_logits outside {0, 1}, low > high or a NaN threshold, connectivity outside {4, 8}, min_area < 1,
+ *   struct_size below this version's (uaps_hysteresis_workspace_bytes: bytes == NULL, non-positive dimension); UAPS_ERANGE C outside
+ *   [1, UAPS_MAX_CLASSES], H * W >= 2^31, B * H * W * 8 >= 2 GiB, scores or the workspace of 2 GiB or more (by dimensions);
+ *   UAPS_EWORKSPACE a workspace smaller than that or not 256-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_HYST_MAX_CLASSES 8
+typedef struct uaps_hysteresis_call {
+    size_t struct_size;
+    int32_t B, C, H, W;                          /* C: channels of scores (not read in the marker form) */
+    int32_t from_logits;
+    int32_t n_classes;
+    int32_t classes[UAPS_HYST_MAX_CLASSES];      /* strictly ascending */
+    float low[UAPS_HYST_MAX_CLASSES], high[UAPS_HYST_MAX_CLASSES];   /* per selected class, low <= high; +-inf allowed */
+    int32_t background;
+    int32_t connectivity;                        /* 4 or 8 */
+    int32_t min_area;                            /* >= 1 */
+    const float* scores;                         /* [B][C][H][W], or NULL: the marker form */
+    const int64_t* mask;                         /* [B][H][W]  (marker form) */
+    const uint8_t* markers;                      /* [B][H][W]  (marker form) */
+    int64_t* out;                                /* [B][H][W] */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_hysteresis_call;
+int uaps_hysteresis_workspace_bytes(int B, int H, int W, size_t* bytes);
+int uaps_hysteresis(const uaps_hysteresis_call* call);
+
+/* ---------------------------------------------------------------------------------------------
  * Defect shape descriptors: csrc/shapes.hip.
  *
  * uaps_shape_descriptors: raw moments, Gray's bit-quad counts and the statistics of an optional plane, per component of the

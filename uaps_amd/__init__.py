@@ -75,6 +75,10 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
                                                     simplified, or COCO / labelme ground truth in sixteenths of a pixel) into a
                                                     label map and a class map, integers only; RasterResult.iou(), fidelity(),
                                                     records(); inference.predict_instances(..., contours=True, raster=True)
+  hysteresis, reconstruct                           hysteresis thresholding of score maps (a region above `low` is kept iff it holds
+                                                    a pixel above `high`) and binary reconstruction of a label map from markers, on
+                                                    the union-find kernels of label_instances; one-channel sigmoid heads included;
+                                                    inference.predict_instances(..., hysteresis=(low, high)), inference.evaluate(..., hysteresis=...)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -123,6 +127,7 @@ from .simplify import simplify_contours, SimplifiedContours
 from . import simplify
 from .raster import rasterize_contours, RasterResult, RingSet, rings_from_polygons, rings_from_coco, RASTER_COLUMNS
 from . import raster
+from .hysteresis import hysteresis, reconstruct      # (hysteresis takes the submodule's name: uaps_amd.hysteresis(scores, low, high))
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

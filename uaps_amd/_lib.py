@@ -176,6 +176,8 @@ SIGNATURES = {
     "uaps_morph_band_rows": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)]),
     "uaps_components_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
     "uaps_components": (C.c_int, [_PTR]),
+    "uaps_hysteresis_workspace_bytes": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_size_t)]),
+    "uaps_hysteresis": (C.c_int, [_PTR]),
     "uaps_shape_descriptors": (C.c_int, [_PTR]),
     "uaps_skeleton_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
     "uaps_skeleton_band_rows": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)]),
@@ -410,6 +412,19 @@ class ComponentsCall(C.Structure):
                 ("kind", C.c_int32 * COMP_MAX_STEPS), ("n", C.c_int32 * COMP_MAX_STEPS), ("n_classes", C.c_int32),
                 ("classes", C.c_int32 * COMP_MAX_CLASSES), ("background", C.c_int32), ("connectivity", C.c_int32),
                 ("mask", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
+HYST_MAX_CLASSES = 8                    # UAPS_HYST_MAX_CLASSES
+
+
+class HysteresisCall(C.Structure):
+    """uaps_hysteresis_call (include/uaps_hip.h): every operand of uaps_hysteresis, size-versioned."""
+    _fields_ = [("struct_size", C.c_size_t), ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("from_logits", C.c_int32), ("n_classes", C.c_int32), ("classes", C.c_int32 * HYST_MAX_CLASSES),
+                ("low", C.c_float * HYST_MAX_CLASSES), ("high", C.c_float * HYST_MAX_CLASSES), ("background", C.c_int32),
+                ("connectivity", C.c_int32), ("min_area", C.c_int32), ("scores", C.c_void_p), ("mask", C.c_void_p),
+                ("markers", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
                 ("stream", C.c_void_p)]
 
 

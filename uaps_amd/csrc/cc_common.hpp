@@ -5,7 +5,8 @@
 //   image(q)     which image of the mask plane q looks at (q itself where a plane is an image; q / n for n virtual planes an image)
 //   fg(v, q)     whether a pixel of value v forms components in plane q at all
 //   key(v, q)    two neighbouring foreground pixels belong together where their keys are equal
-// and FLAG of cc_flatten_area: whether a component that has a pixel on the image border gets bit 31 of its area word raised.
+// and the MARK of cc_flatten_area: which pixels raise bit 31 of their component's area word (NoMark: none; BorderMark: those on the
+// image border; a user's own: hysteresis.hip marks the seeds of its code map).
 //
 // Every parent word holds the plane-local index of an earlier or equal pixel of the same component (-1: not foreground), only ever
 // decreases, and a walk ends at the word that names itself: the component's first pixel in raster order.  No workgroup waits for
@@ -18,7 +19,7 @@
 namespace uaps {
 namespace cc {
 constexpr int kTW = 16, kTH = 16, kTile = kTW * kTH, kPer = kTile / kThreads;   // pixels of a tile per lane
-constexpr unsigned kBorderBit = 0x80000000u;                                    // of an area word (H * W < 2^31 leaves it free)
+constexpr unsigned kBorderBit = 0x80000000u;                                    // the mark bit of an area word (H * W < 2^31 leaves it free)
 constexpr unsigned kAreaMask = 0x7fffffffu;
 
 __device__ __forceinline__ int ld_agent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -189,6 +190,22 @@ __device__ __forceinline__ int run_end(unsigned long long heads, int lane) {
 constexpr int kSpan = 16;
 inline int span_grid(long N) { return (int)((N + (long)kThreads * kSpan - 1) / ((long)kThreads * kSpan)); }
 
+// The mark policy of cc_flatten_area: mark(n, i) of a foreground pixel -- n its index over all planes, i its plane-local index --
+// says whether the pixel raises kBorderBit of its component's area word.  kOn == false: no flag is formed at all.
+struct NoMark {
+    static constexpr bool kOn = false;
+    __device__ __forceinline__ bool operator()(long, long) const { return false; }
+};
+// the pixels of row 0, row H - 1, column 0 and column W - 1
+struct BorderMark {
+    static constexpr bool kOn = true;
+    int H, W;
+    __device__ __forceinline__ bool operator()(long, long i) const {
+        const int y = (int)(i / W), x = (int)(i - (long)y * W);
+        return y == 0 || y == H - 1 || x == 0 || x == W - 1;
+    }
+};
+
 template <bool FLAG>
 __device__ __forceinline__ void cc_send(int* word, int n, bool border) {
     atomicAdd(word, n);
@@ -200,12 +217,14 @@ __device__ __forceinline__ void cc_send(int* word, int n, bool border) {
 // wherever in the group they sit -- are counted by one ballot and carried on by the wave over its kSpan groups while the leading root
 // stays the same; the other roots of the group send one atomicAdd per run of equal roots.  So a component that fills rows, and
 // equally one that is porous (class noise; the complement of a class in hole filling), costs one atomic per kSpan * 64 pixels and
-// not one per run: thousands of adds to ONE word serialise at the memory side.  FLAG: what is sent for pixels among which one lies in
-// row 0, row H - 1, column 0 or column W - 1 also raises kBorderBit of that word, once per send.  N = Q * HW pixels; HW = H * W.
+// not one per run: thousands of adds to ONE word serialise at the memory side.  Mark::kOn: what is sent for pixels among which one is
+// marked also raises kBorderBit of that word, once per send -- on BOTH paths, the wave-carried leading root and the per-run adds of
+// the other roots: a mark may sit on any pixel of a component, not only on the border.  N = Q * HW pixels; HW = H * W.
 // `roots` may be `parent` itself (components.hip): a word is then overwritten by its own lane alone, with its root, while other
 // lanes may still walk through it -- they read the old parent or the root, and either is an ancestor in the same component.
-template <bool FLAG>
-__device__ __forceinline__ void cc_flatten_area(const int* parent, int* roots, int* area, long HW, long N, int H, int W) {
+template <typename Mark>
+__device__ __forceinline__ void cc_flatten_area(const int* parent, int* roots, int* area, long HW, long N, const Mark mark) {
+    constexpr bool FLAG = Mark::kOn;
     const int lane = threadIdx.x & 63;
     const long w0 = ((long)blockIdx.x * kWaves + (threadIdx.x >> 6)) * (kSpan * 64);
     long pend_b = -1;
@@ -225,10 +244,7 @@ __device__ __forceinline__ void cc_flatten_area(const int* parent, int* roots, i
             r = par[i];
             if (r >= 0) r = uf_find_plain(par, r);
             roots[n] = r;
-            if (FLAG && r >= 0) {
-                const int y = (int)(i / W), x = (int)(i - (long)y * W);
-                edge = y == 0 || y == H - 1 || x == 0 || x == W - 1;
-            }
+            if (FLAG && r >= 0) edge = mark(n, i);
         }
         const int prev = __shfl_up(r, 1, 64);
         const bool head = lane == 0 || prev != r || i == 0;

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(kThreads) void comp_seam_holes_kernel(HoleArgs a) {
 
 // in place: words[n] parent -> root (cc_common.hpp, cc_flatten_area, on why that is sound)
 __global__ __launch_bounds__(kThreads) void comp_flatten_kernel(int* words, int* area, long HW, long N, int H, int W) {
-    cc_flatten_area<true>(words, words, area, HW, N, H, W);
+    cc_flatten_area(words, words, area, HW, N, BorderMark{H, W});
 }
 
 struct ApplyArgs {

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kThreads) void tile_label_kernel(LabelArgs a) {
 __global__ __launch_bounds__(kThreads) void seam_merge_kernel(LabelArgs a) { cc_seam_merge(a); }
 
 __global__ __launch_bounds__(kThreads) void flatten_area_kernel(const int* __restrict__ parent, int* __restrict__ roots, int* area, long HW, long N) {
-    cc_flatten_area<false>(parent, roots, area, HW, N, 0, 0);
+    cc_flatten_area(parent, roots, area, HW, N, NoMark());
 }
 
 struct NumberArgs {

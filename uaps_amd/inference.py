@@ -172,6 +172,8 @@ def _forward(model, images, tta, tiled_kw, want) -> _Forward:
         return _Forward(r.probs, False, r.mask, r.conf, tuple(r.maps), None)
     mask, heads = predict(model, images) if not tta or "heads" in want else (None, None)
     if tta:
+        if heads is not None and heads[0].shape[1] == 1:
+            raise ValueError("tta: a one-channel sigmoid model has no form under tta (the fold kernel takes 2..8 classes)")
         from .tta import DEFAULT_SCALES, predict_tta
         r = predict_tta(model, images, scales=DEFAULT_SCALES if tta is True else tuple(tta), want=maps)
         return _Forward(r.probs, False, r.mask, r.conf, (), heads)
@@ -191,6 +193,30 @@ def _cleaned(mask: torch.Tensor, cleanup, num_classes: int, components=None) -> 
     return mask
 
 
+_HYSTERESIS_KEYS = ("low", "high", "classes", "background", "min_area")
+
+
+def _hysteresis_kwargs(hysteresis, what: str, own_connectivity: bool) -> dict:
+    """The hysteresis.hysteresis keywords of a `hysteresis` argument: a (low, high) pair, or a dict with "low" and "high" and any of
+    classes, background and min_area -- and connectivity where the caller has none of its own (own_connectivity)."""
+    if isinstance(hysteresis, dict):
+        kw = dict(hysteresis)
+        allowed = _HYSTERESIS_KEYS + (("connectivity",) if own_connectivity else ())
+        if "low" not in kw or "high" not in kw or not set(kw) <= set(allowed):
+            raise ValueError(f"{what}: a hysteresis dict holds \"low\" and \"high\" and any of {allowed[2:]}")
+    elif isinstance(hysteresis, (tuple, list)) and len(hysteresis) == 2:
+        kw = {"low": hysteresis[0], "high": hysteresis[1]}
+    else:
+        raise ValueError(f"{what}: hysteresis is a (low, high) pair or a dict of hysteresis keywords")
+    return kw
+
+
+def _hysteresis_mask(f: "_Forward", kw: dict, **more) -> torch.Tensor:
+    """The hysteresis mask of a forward's scored maps: from the logits on the plain path, from the probability maps under tta / tiled."""
+    from .hysteresis import hysteresis as hysteresis_mask
+    return hysteresis_mask(f.scored, from_logits=f.is_logits, **{**kw, **more})
+
+
 def _one_hot_maps(mask: torch.Tensor, num_classes: int) -> torch.Tensor:
     """float32 [B,C,H,W] maps whose arg-max is `mask`: what the scoring kernels take in place of logits."""
     return torch.nn.functional.one_hot(mask, num_classes).permute(0, 3, 1, 2).contiguous().float()
@@ -198,7 +224,8 @@ def _one_hot_maps(mask: torch.Tensor, num_classes: int) -> torch.Tensor:
 
 @torch.no_grad()
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None, tiled=None,
-             surface=None, instances=None, curves=None, cleanup=None, components=None, detection=None) -> Dict[str, float]:
+             surface=None, instances=None, curves=None, cleanup=None, components=None, detection=None,
+             hysteresis=None) -> Dict[str, float]:
     """The score table of the main head over `batches` of (images, labels): scoring.ConfusionScorer's mIoU, mDice, pixel accuracy
     and "images", then the keys of every family that is switched on, in this order (each scorer of scoring.py documents its own).
     tta=True, or a tuple of scales: the multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main
@@ -210,14 +237,19 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     surface (scoring.SurfaceScorer), instances (scoring.InstanceScorer): True or a dict of keywords, off for every falsy value.
     curves (scoring.CurveScorer): True or a dict of keywords -- an empty one asks for the defaults; off for None and False.
     detection (scoring.DetectionScorer): True or a dict of keywords, off for every falsy value; it scores the defects of the masked
-    maps' arg-max like instances=, its keys come last."""
+    maps' arg-max like instances=, its keys come last.
+    hysteresis: a (low, high) pair or a dict of hysteresis.hysteresis keywords (low, high, classes, background, min_area,
+    connectivity): the hysteresis mask of the scored maps (from the logits on the plain path, from the probability maps under tta /
+    tiled) replaces the arg-max as the start of the clean-up chain, and counts as a clean-up: scoring.CleanScorer's two keys are
+    added and surface=, instances= and detection= score that mask.  Models of two classes and more; None: off."""
     if cleanup is not None:
         from .morphology import check_steps
         cleanup = check_steps(cleanup)
     if components is not None:
         from .components import check_steps as check_component_steps
         components = check_component_steps(components)
-    clean = cleanup is not None or components is not None
+    hyst_kw = _hysteresis_kwargs(hysteresis, "evaluate", True) if hysteresis is not None else None
+    clean = cleanup is not None or components is not None or hyst_kw is not None
     curve = scoring.CurveScorer(curves, plain_path=not (tta or tiled)) if curves is not None and curves is not False else None
     tiled_kw = _tiled_kwargs(tiled, tta, "evaluate") if tiled else None
     base = scoring.ConfusionScorer()
@@ -230,7 +262,10 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         masked = f.scored
         if clean:
             Cn = f.scored.shape[1]
-            masked = _one_hot_maps(_cleaned(torch.argmax(f.scored, dim=1), cleanup, Cn, components), Cn)
+            if hyst_kw is not None and Cn == 1:
+                raise ValueError("evaluate: hysteresis= scores models of two classes and more (one-channel sigmoid heads: bin_confusion)")
+            start = torch.argmax(f.scored, dim=1) if hyst_kw is None else _hysteresis_mask(f, hyst_kw)
+            masked = _one_hot_maps(_cleaned(start, cleanup, Cn, components), Cn)
         batch = scoring.Batch(f.scored, f.is_logits, masked, y, f.heads)
         for s in scorers:
             s.update(batch)
@@ -251,7 +286,7 @@ def _with_shapes(inst, shapes, connectivity: int):
 @torch.no_grad()
 def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, tiled=None, min_area: int = 1, connectivity: int = 8,
                       max_instances: int = 256, cleanup=None, components=None, shapes=False, skeleton=False, hull=False,
-                      contours=False, simplify=None, raster=False):
+                      contours=False, simplify=None, raster=False, hysteresis=None):
     """Defects instead of pixels: instances.label_instances on the main head's arg-max mask, with maps = (confidence, uncertainty).
     The confidence is the main head's largest softmax; with tta (True, or a tuple of scales) mask and confidence are those of
     tta.predict_tta.  The uncertainty is consistency.uncertainty_map(main, aux1) of the plain forward where the model has an auxiliary
@@ -279,7 +314,13 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     ContourResult.  Under all three paths.
     raster=True (needs contours=True): a raster.RasterResult instead -- raster.rasterize_contours of what the same call returns
     without raster= (the ContourResult, or with simplify= the SimplifiedContours), filled against the instance labels: its
-    `.contours` holds that result, iou() and fidelity() say what every polygon still covers of its defect.  Under all three paths."""
+    `.contours` holds that result, iou() and fidelity() say what every polygon still covers of its defect.  Under all three paths.
+    hysteresis=(low, high), or a dict of hysteresis.hysteresis keywords (low, high, classes, background, min_area): the mask that is
+    cleaned and labelled is the hysteresis mask instead of the arg-max -- of the main head's logits on the plain path, of the
+    probability maps under tta and tiled -- at the call's connectivity, before the cleanup= and components= chains; every other
+    keyword works as before.  A one-channel sigmoid model needs it (ValueError without) and has the plain path alone: the mask is
+    class 1 where the rule says so, the confidence is max(p, 1 - p) of the sigmoid, later steps see two classes and no uncertainty
+    map is formed."""
     from . import instances
     if raster is not False and raster is not True:
         raise ValueError("predict_instances: raster is False or True")
@@ -302,24 +343,33 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     if components is not None:
         from .components import check_steps as check_component_steps
         components = check_component_steps(components)
-    tiled_kw, want = None, ("mask", "conf", "heads")
+    hyst_kw = _hysteresis_kwargs(hysteresis, "predict_instances", False) if hysteresis is not None else None
+    tiled_kw, want = None, ("mask", "conf", "heads") + (("probs",) if tta and hyst_kw is not None else ())
     if tiled:
         # (the class count of the clean-up is the blended maps' channel count: they are asked for beside the mask then)
-        tiled_kw, want = _tiled_kwargs(tiled, tta, "predict_instances"), ("mask", "conf") + (("probs",) if clean or skeleton is not False else ())
+        tiled_kw = _tiled_kwargs(tiled, tta, "predict_instances")
+        want = ("mask", "conf") + (("probs",) if clean or skeleton is not False or hyst_kw is not None else ())
         tiled_kw.setdefault("uncertainty", "auto")
     f = _forward(model, images, tta, tiled_kw, want)
-    maps = (f.conf,) + f.maps
-    if f.heads is not None and len(f.heads) >= 2:
+    num_classes = (f.scored if f.heads is None else f.heads[0]).shape[1] if f.scored is not None or f.heads is not None else None
+    binary = num_classes == 1                   # a one-channel sigmoid head (the plain path: tta and tiled have refused it)
+    if binary and hyst_kw is None:
+        raise ValueError("predict_instances: a one-channel sigmoid model has no arg-max mask: pass hysteresis=(low, high)")
+    conf = f.conf
+    if binary:
+        p = torch.sigmoid(f.scored)[:, 0]
+        conf, num_classes = torch.maximum(p, 1.0 - p), 2
+    maps = (conf,) + f.maps
+    if f.heads is not None and len(f.heads) >= 2 and not binary:
         maps += (consistency.uncertainty_map(f.heads[0], f.heads[1]),)
-    mask = f.mask
+    mask = f.mask if hyst_kw is None else _hysteresis_mask(f, hyst_kw, connectivity=connectivity)
     if clean:
-        mask = _cleaned(mask, cleanup, (f.scored if f.heads is None else f.heads[0]).shape[1], components)
+        mask = _cleaned(mask, cleanup, num_classes, components)
     inst = instances.label_instances(mask, maps, connectivity=connectivity, min_area=min_area, max_instances=max_instances)
     if skeleton is False:
         res = _with_shapes(inst, shapes, connectivity)
     else:
         from .skeleton import skeletonize, skeleton_descriptors
-        num_classes = (f.scored if f.heads is None else f.heads[0]).shape[1]
         skel = skeletonize(mask, num_classes, **(skeleton if isinstance(skeleton, dict) else {}))
         stats = skeleton_descriptors(inst, skel)
         res = stats._replace(shapes=_with_shapes(inst, shapes, connectivity)) if shapes else stats

@@ -281,6 +281,8 @@ def predict_tiled(model: torch.nn.Module, images: torch.Tensor, tile=(256, 256),
         if uncertainty:
             out = model(t)
             heads = out if isinstance(out, (tuple, list)) else (out,)
+            if heads[0].dim() == 4 and heads[0].shape[1] == 1:        # (tile_fold's refusal, before the uncertainty kernel sees the pair)
+                raise ValueError("predict_tiled: 2..8 classes (one-channel sigmoid heads have no form here)")
             if len(heads) < 2:
                 if uncertainty != "auto":
                     raise ValueError("the uncertainty map needs an auxiliary head")

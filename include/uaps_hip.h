@@ -1514,6 +1514,75 @@ int uaps_hysteresis_workspace_bytes(int B, int H, int W, size_t* bytes);
 int uaps_hysteresis(const uaps_hysteresis_call* call);
 
 /* ---------------------------------------------------------------------------------------------
+ * Splitting of touching defects: csrc/split.hip (the labelling passes: csrc/cc_common.hpp; numbering and table: csrc/instances.hip).
+ *
+ * uaps_split_instances: the components of uaps_label_instances (source_labels int32 [B, H, W], source_table int64
+ *   [B, source_rows, 9]) cut into the geodesic zones of influence of their MARKERS.  H, W <= UAPS_SPLIT_MAX_EXTENT.
+ *   Marker pixels: a pixel with source label > 0 and, distance form (distance != NULL, markers NULL), distance[pixel] >= d2 --
+ *     distance int32 [B, H, W], usually uaps_edt_sq of the source labels -- or, marker form (markers != NULL, distance NULL),
+ *     markers[pixel] != 0 (uint8 [B, H, W]; d2 is not read).
+ *   Markers: the maximal sets of marker pixels of ONE source label under `connectivity` (4 or 8) with at least min_marker_area
+ *     pixels.  A marker's id is the image-local raster index of its first pixel, plus 1.
+ *   Owners: round 0, a pixel of a marker owns that marker's id, every other pixel 0.  One synchronous round: every pixel with source
+ *     label > 0 and owner 0 takes the smallest non-zero owner among its neighbours (under `connectivity`) of the same source label,
+ *     all pixels reading the state of the round's start.  The result is the state after min(max_iters, rounds until nothing
+ *     changes) rounds; converged[b] (uint8 [B]) = 1 iff image b is at the fixed point.
+ *   Pieces: maximal connected sets (under `connectivity`) of equal (source label, owner), numbered and tabulated exactly as
+ *     uaps_label_instances does it: labels int32 [B, H, W], count int32 [B] (complete whatever max_instances is), table int64
+ *     [B, max_instances, 9] with the same columns, pieces below min_area pixels removed, map0 / map1 summed as there.  The class
+ *     column is source_table's class of the piece's source label, -1 for a source label above source_rows.
+ *     parent int32 [B, max_instances]: the source label of piece k, 0 in rows without a piece.  pieces int32 [B, source_rows]: how
+ *     many rows of `parent` name each source label.
+ *   Launches: a classify pass (the marker code map), the three labelling passes of cc_common.hpp on it, an init pass (the owner plane),
+ *   ceil(max_iters / S) growth launches of S rounds each on tiles staged in LDS -- S = sub_iters, 0: the default; a launch returns
+ *   at once once its image stopped changing -- a check pass, a code pass, the seven launches of uaps_label_instances on the code map
+ *   (label << 32) | owner and one fix-up pass over the table rows.  Integer atomics only: the same bits from run to run and for every
+ *   sub_iters, band_rows and tile_cols (0: the plan's; uaps_split_band_rows answers what that is).  The call does not synchronise;
+ *   everything the workspace carries is written inside the call before it is read.
+ *   workspace: uaps_split_workspace_bytes(B, H, W) bytes (about 24 a pixel), 256-byte aligned, the call's alone until it has run.
+ * Errors (nothing launched): UAPS_EINVAL null struct, a null operand other than map0 / map1, both or neither of distance and
+ *   markers, map1 without map0, non-positive dimension, connectivity outside {4, 8}, min_area, min_marker_area, max_instances or
+ *   source_rows < 1, d2 < 0, max_iters outside [1, UAPS_SPLIT_MAX_ITERS], sub_iters outside [0, UAPS_SPLIT_MAX_SUB_ITERS], negative
+ *   band_rows or tile_cols, struct_size below this version's; UAPS_ERANGE H or W above UAPS_SPLIT_MAX_EXTENT, B * H * W * 8 >= 2 GiB,
+ *   a table or the workspace of 2 GiB or more (by dimensions), a forced tile that does not fit 64 KiB of LDS with its halo;
+ *   UAPS_EWORKSPACE a workspace smaller than uaps_split_workspace_bytes or not 256-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define UAPS_SPLIT_MAX_EXTENT 4096
+#define UAPS_SPLIT_MAX_ITERS 65536
+#define UAPS_SPLIT_MAX_SUB_ITERS 16
+typedef struct uaps_split_call {
+    size_t struct_size;
+    int32_t B, H, W;
+    int32_t connectivity;                        /* 4 or 8: the one the source was labelled with */
+    int32_t d2;                                  /* distance form: >= 0 */
+    int32_t min_marker_area;                     /* >= 1 */
+    int32_t max_iters;                           /* 1 .. UAPS_SPLIT_MAX_ITERS */
+    int32_t sub_iters;                           /* rounds a launch; 0: the default */
+    int32_t band_rows, tile_cols;                /* owned rows and columns of a tile; 0: the plan's */
+    int32_t min_area;                            /* >= 1, of the pieces */
+    int32_t max_instances;                       /* rows of table and parent */
+    int32_t source_rows;                         /* rows of source_table and pieces */
+    const int32_t* source_labels;                /* [B][H][W] */
+    const int64_t* source_table;                 /* [B][source_rows][9] */
+    const int32_t* distance;                     /* [B][H][W], or NULL: the marker form */
+    const uint8_t* markers;                      /* [B][H][W], or NULL: the distance form */
+    const float* map0;                           /* [B][H][W] or NULL */
+    const float* map1;
+    int32_t* labels;                             /* [B][H][W] */
+    int32_t* count;                              /* [B] */
+    int64_t* table;                              /* [B][max_instances][9] */
+    int32_t* parent;                             /* [B][max_instances] */
+    int32_t* pieces;                             /* [B][source_rows] */
+    uint8_t* converged;                          /* [B] */
+    void* workspace;
+    size_t workspace_bytes;
+    uaps_stream_t stream;
+} uaps_split_call;
+int uaps_split_workspace_bytes(int B, int H, int W, size_t* bytes);
+int uaps_split_band_rows(int H, int W, int sub_iters, int* rows, int* cols);
+int uaps_split_instances(const uaps_split_call* call);
+
+/* ---------------------------------------------------------------------------------------------
  * Defect shape descriptors: csrc/shapes.hip.
  *
  * uaps_shape_descriptors: raw moments, Gray's bit-quad counts and the statistics of an optional plane, per component of the

@@ -79,6 +79,10 @@ Public surface (mirrors the names the reference's UAPS_train.py imports):
                                                     a pixel above `high`) and binary reconstruction of a label map from markers, on
                                                     the union-find kernels of label_instances; one-channel sigmoid heads included;
                                                     inference.predict_instances(..., hysteresis=(low, high)), inference.evaluate(..., hysteresis=...)
+  split_instances, SplitResult                      touching defects cut apart: cores by the distance transform (or the caller's
+                                                    markers), grown back inside the defect in synchronous rounds on LDS tiles, the
+                                                    pieces numbered and tabulated like label_instances' components;
+                                                    inference.predict_instances(..., split=radius), inference.evaluate(..., split=...)
 """
 from .ramps import sigmoid_rampup, get_current_consistency_weight
 from .losses import (dice_loss, ce_loss, uaps_sup_loss, uaps_unsup_loss, uaps_step_loss, uaps_pair_loss, unsup_scalars,
@@ -128,6 +132,8 @@ from . import simplify
 from .raster import rasterize_contours, RasterResult, RingSet, rings_from_polygons, rings_from_coco, RASTER_COLUMNS
 from . import raster
 from .hysteresis import hysteresis, reconstruct      # (hysteresis takes the submodule's name: uaps_amd.hysteresis(scores, low, high))
+from .split import split_instances, SplitResult
+from . import split
 from . import augment, cct_dct, conv, cps, data, dist, graph, inference, mean_teacher, optim, seg_losses, sibling, ucc
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -178,6 +178,9 @@ SIGNATURES = {
     "uaps_components": (C.c_int, [_PTR]),
     "uaps_hysteresis_workspace_bytes": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_size_t)]),
     "uaps_hysteresis": (C.c_int, [_PTR]),
+    "uaps_split_workspace_bytes": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_size_t)]),
+    "uaps_split_band_rows": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "uaps_split_instances": (C.c_int, [_PTR]),
     "uaps_shape_descriptors": (C.c_int, [_PTR]),
     "uaps_skeleton_workspace_bytes": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_size_t)]),
     "uaps_skeleton_band_rows": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)]),
@@ -428,7 +431,21 @@ class HysteresisCall(C.Structure):
                 ("stream", C.c_void_p)]
 
 
-SHAPE_COLUMNS, SHAPE_MAX_EXTENT, SHAPE_LDS_ROWS = 11, 16384, 256      # UAPS_SHAPE_COLUMNS, UAPS_SHAPE_MAX_EXTENT, UAPS_SHAPE_LDS_ROWS
+SPLIT_MAX_EXTENT, SPLIT_MAX_ITERS, SPLIT_MAX_SUB_ITERS = 4096, 65536, 16     # UAPS_SPLIT_*
+
+
+class SplitCall(C.Structure):
+    """uaps_split_call (include/uaps_hip.h): every operand of uaps_split_instances, size-versioned."""
+    _fields_ = [("struct_size", C.c_size_t), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("connectivity", C.c_int32),
+                ("d2", C.c_int32), ("min_marker_area", C.c_int32), ("max_iters", C.c_int32), ("sub_iters", C.c_int32),
+                ("band_rows", C.c_int32), ("tile_cols", C.c_int32), ("min_area", C.c_int32), ("max_instances", C.c_int32),
+                ("source_rows", C.c_int32), ("source_labels", C.c_void_p), ("source_table", C.c_void_p), ("distance", C.c_void_p),
+                ("markers", C.c_void_p), ("map0", C.c_void_p), ("map1", C.c_void_p), ("labels", C.c_void_p), ("count", C.c_void_p),
+                ("table", C.c_void_p), ("parent", C.c_void_p), ("pieces", C.c_void_p), ("converged", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+SHAPE_COLUMNS, SHAPE_MAX_EXTENT, SHAPE_LDS_ROWS = 11, 16384, 256     # UAPS_SHAPE_COLUMNS, UAPS_SHAPE_MAX_EXTENT, UAPS_SHAPE_LDS_ROWS
 
 
 class ShapeCall(C.Structure):

@@ -34,6 +34,7 @@
 // "equal values belong together, the background forms nothing" and without the border flag.
 #include <string.h>
 #include "cc_common.hpp"
+#include "instances_launch.hpp"
 
 namespace {
 using uaps::kThreads; using uaps::kWaves; using uaps::kTooBig; using uaps::grid_for; using uaps::align256;
@@ -373,7 +374,14 @@ extern "C" int uaps_label_instances(const uaps_instances_call* call) {
     if (rc) return rc;
     if ((double)c.B * c.max_instances * 72.0 >= kTooBig) return UAPS_ERANGE;
     if (c.workspace_bytes < workspace_for(c.B, c.H, c.W)) return UAPS_EWORKSPACE;
+    return uaps::label_launches(c);
+}
 
+// The launches of uaps_label_instances on a call whose every check has passed (instances_launch.hpp): split.hip runs them on its own
+// code map, with a part of its workspace as theirs.
+size_t uaps::label_workspace_bytes(int B, int H, int W) { return workspace_for(B, H, W); }
+
+int uaps::label_launches(const uaps_instances_call& c) {
     const long HW = (long)c.H * c.W, N = (long)c.B * HW;
     const int chunks = (int)chunks_of(HW);
     char* ws = static_cast<char*>(c.workspace);

@@ -225,7 +225,7 @@ def _one_hot_maps(mask: torch.Tensor, num_classes: int) -> torch.Tensor:
 @torch.no_grad()
 def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], tta=None, tiled=None,
              surface=None, instances=None, curves=None, cleanup=None, components=None, detection=None,
-             hysteresis=None) -> Dict[str, float]:
+             hysteresis=None, split=None) -> Dict[str, float]:
     """The score table of the main head over `batches` of (images, labels): scoring.ConfusionScorer's mIoU, mDice, pixel accuracy
     and "images", then the keys of every family that is switched on, in this order (each scorer of scoring.py documents its own).
     tta=True, or a tuple of scales: the multi-scale + flip sum of probability maps (tta.predict_tta) is scored instead of the main
@@ -241,7 +241,10 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
     hysteresis: a (low, high) pair or a dict of hysteresis.hysteresis keywords (low, high, classes, background, min_area,
     connectivity): the hysteresis mask of the scored maps (from the logits on the plain path, from the probability maps under tta /
     tiled) replaces the arg-max as the start of the clean-up chain, and counts as a clean-up: scoring.CleanScorer's two keys are
-    added and surface=, instances= and detection= score that mask.  Models of two classes and more; None: off."""
+    added and surface=, instances= and detection= score that mask.  Models of two classes and more; None: off.
+    split: a radius or a dict of split.split_instances keywords (radius, min_marker_area, max_iters): the instances= and detection=
+    scorers cut the PREDICTION's defects with split.split_instances before they match them (the ground truth is left alone); needs
+    one of the two.  None: off, and every key keeps its value."""
     if cleanup is not None:
         from .morphology import check_steps
         cleanup = check_steps(cleanup)
@@ -249,13 +252,19 @@ def evaluate(model: torch.nn.Module, batches: Iterable[Tuple[torch.Tensor, torch
         from .components import check_steps as check_component_steps
         components = check_component_steps(components)
     hyst_kw = _hysteresis_kwargs(hysteresis, "evaluate", True) if hysteresis is not None else None
+    split_kw = None
+    if split is not None:
+        from .split import split_keywords
+        split_kw = split_keywords(split, "evaluate")
+        if not instances and not detection:
+            raise ValueError("evaluate: split= cuts the defects the instances= and detection= scorers match: switch one of them on")
     clean = cleanup is not None or components is not None or hyst_kw is not None
     curve = scoring.CurveScorer(curves, plain_path=not (tta or tiled)) if curves is not None and curves is not False else None
     tiled_kw = _tiled_kwargs(tiled, tta, "evaluate") if tiled else None
     base = scoring.ConfusionScorer()
     scorers = [base, scoring.CleanScorer() if clean else None, scoring.SurfaceScorer(surface) if surface else None,
-               scoring.InstanceScorer(instances) if instances else None, curve,
-               scoring.DetectionScorer(detection) if detection else None]
+               scoring.InstanceScorer(instances, split_kw) if instances else None, curve,
+               scoring.DetectionScorer(detection, split_kw) if detection else None]
     scorers = [s for s in scorers if s is not None]
     for x, y in batches:
         f = _forward(model, x, tta, tiled_kw, ("probs",))
@@ -286,7 +295,7 @@ def _with_shapes(inst, shapes, connectivity: int):
 @torch.no_grad()
 def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None, tiled=None, min_area: int = 1, connectivity: int = 8,
                       max_instances: int = 256, cleanup=None, components=None, shapes=False, skeleton=False, hull=False,
-                      contours=False, simplify=None, raster=False, hysteresis=None):
+                      contours=False, simplify=None, raster=False, hysteresis=None, split=None):
     """Defects instead of pixels: instances.label_instances on the main head's arg-max mask, with maps = (confidence, uncertainty).
     The confidence is the main head's largest softmax; with tta (True, or a tuple of scales) mask and confidence are those of
     tta.predict_tta.  The uncertainty is consistency.uncertainty_map(main, aux1) of the plain forward where the model has an auxiliary
@@ -320,7 +329,12 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     probability maps under tta and tiled -- at the call's connectivity, before the cleanup= and components= chains; every other
     keyword works as before.  A one-channel sigmoid model needs it (ValueError without) and has the plain path alone: the mask is
     class 1 where the rule says so, the confidence is max(p, 1 - p) of the sigmoid, later steps see two classes and no uncertainty
-    map is formed."""
+    map is formed.
+    split=radius, or a dict of split.split_instances keywords (radius, min_marker_area, max_iters): touching defects are cut apart --
+    split.split_instances of the InstanceResult, at the call's connectivity and min_area and with the same confidence / uncertainty
+    maps, after label_instances and both clean-up chains and before shapes= / skeleton= / hull= / contours=, which then describe the
+    PIECES.  What takes the InstanceResult's place is the pieces' (a split.SplitInstances: an InstanceResult whose `.split` holds
+    the SplitResult with parent, pieces, converged and the unsplit source).  Under all three paths."""
     from . import instances
     if raster is not False and raster is not True:
         raise ValueError("predict_instances: raster is False or True")
@@ -344,6 +358,10 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
         from .components import check_steps as check_component_steps
         components = check_component_steps(components)
     hyst_kw = _hysteresis_kwargs(hysteresis, "predict_instances", False) if hysteresis is not None else None
+    split_kw = None
+    if split is not None:
+        from . import split as split_mod
+        split_kw = split_mod.split_keywords(split, "predict_instances")
     tiled_kw, want = None, ("mask", "conf", "heads") + (("probs",) if tta and hyst_kw is not None else ())
     if tiled:
         # (the class count of the clean-up is the blended maps' channel count: they are asked for beside the mask then)
@@ -366,6 +384,10 @@ def predict_instances(model: torch.nn.Module, images: torch.Tensor, *, tta=None,
     if clean:
         mask = _cleaned(mask, cleanup, num_classes, components)
     inst = instances.label_instances(mask, maps, connectivity=connectivity, min_area=min_area, max_instances=max_instances)
+    if split_kw is not None:
+        cut = split_mod.split_instances(inst, maps=maps, connectivity=connectivity, min_area=min_area, **split_kw)
+        inst = split_mod.SplitInstances(*cut.instances)
+        inst.split = cut
     if skeleton is False:
         res = _with_shapes(inst, shapes, connectivity)
     else:

@@ -35,6 +35,15 @@ def _label_keywords(kw) -> dict:
     return {k: kw[k] for k in ("min_area", "connectivity", "max_instances") if k in kw}
 
 
+def _split(pred, maps, lab: Dict, split):
+    """The prediction's defects, cut by split.split_instances where evaluate(split=) asks for it (the pieces keep the labelling's
+    connectivity, min_area and rows); `pred` itself without."""
+    if split is None:
+        return pred
+    from .split import split_instances
+    return split_instances(pred, maps=maps, connectivity=lab.get("connectivity", 8), min_area=lab.get("min_area", 1), **split).instances
+
+
 class ConfusionScorer:
     """The score table of notebook cell 25: mIoU, mDice and pixel accuracy of the scored maps' arg-max computed image by image
     (utilities/metrics.py conventions) and averaged over the images, in percent, and "images", their number."""
@@ -108,15 +117,16 @@ class InstanceScorer:
     "defects_pred" and "instance_images_skipped" (images with more defects than max_instances on either side are left out)."""
     KEYS = ("classes", "connectivity", "iou_threshold", "max_instances", "min_area")
 
-    def __init__(self, instances):
+    def __init__(self, instances, split=None):
         self.kw = _keywords(instances, self.KEYS, "instances")
+        self.split = split                                   # split.split_instances keywords: the prediction's defects are cut first
         self.sums = []                                       # per batch matching.MatchResult.sums: float64 [K,7] on the device
 
     def update(self, batch: Batch) -> None:
         from .instances import label_instances
         from .matching import match_instances
         lab = _label_keywords(self.kw)
-        pred = label_instances(torch.argmax(batch.masked, dim=1), **lab)
+        pred = _split(label_instances(torch.argmax(batch.masked, dim=1), **lab), (), lab, self.split)
         target = label_instances(batch.labels.to(torch.int64), **lab)
         match = match_instances(pred, target, batch.masked.shape[1], iou_threshold=self.kw.get("iou_threshold", 0.5))
         self.sums.append(match.sums(self.kw.get("classes")))
@@ -142,9 +152,10 @@ class DetectionScorer:
     list) and "detection_images_skipped" (images with more defects than max_instances on either side are left out)."""
     KEYS = ("classes", "connectivity", "iou_thresholds", "max_dets", "max_instances", "min_area")
 
-    def __init__(self, detection):
+    def __init__(self, detection, split=None):
         from .detection import COCO_THRESHOLDS, per_mille
         self.kw = _keywords(detection, self.KEYS, "detection")
+        self.split = split
         self.thresholds = tuple(k / 1000.0 for k in per_mille(self.kw.get("iou_thresholds", COCO_THRESHOLDS)))
         self.parts, self.num_classes = [], 0                 # per batch detection.DetectionSums on the device
 
@@ -154,7 +165,7 @@ class DetectionScorer:
         lab = _label_keywords(self.kw)
         probs = torch.softmax(batch.scored.float(), dim=1) if batch.from_logits else batch.scored.float()
         conf = probs.amax(dim=1).contiguous()
-        pred = label_instances(torch.argmax(batch.masked, dim=1), maps=(conf,), **lab)
+        pred = _split(label_instances(torch.argmax(batch.masked, dim=1), maps=(conf,), **lab), (conf,), lab, self.split)
         target = label_instances(batch.labels.to(torch.int64), **lab)
         self.num_classes = batch.masked.shape[1]
         res = detection_match(pred, target, self.num_classes, iou_thresholds=self.thresholds, max_dets=self.kw.get("max_dets"))
